@@ -34,6 +34,12 @@ torch.distributed.run (WORLD_SIZE set, as the driver launches it) each process i
 ``--backend gloo --dry-run`` walks the same launcher and the same tile sharding + exchange on host tensors without
 a GPU (tests/test_bench_launcher.py).
 
+A plain run measures the headline and nothing else: set-up, warm-up, the timed steps, the result line.  ``--full``
+adds the side measurements (``pipelined``, ``k1_reference_path``, ``inr_path``, ``scaling_model``, ``cpu_baseline`` +
+``parity``, and for N > 1 the serialised ``exchange``); the ``--no-*`` options leave single ones out of it.
+``--dump-outputs DIR`` writes the frame the last timed step rendered (rank 0's assembled frame at N > 1) to
+``DIR/frame.npy`` (float32, H x W x RGBA); inputs are seeded, so two builds can be compared output for output.
+
 Prints ONE JSON line (rank 0).
 """
 from __future__ import annotations
@@ -58,6 +64,7 @@ BYTES_PER_SAMPLE = 32         # 8 taps x 4 B, one fp32 channel          (SURVEY.
 BYTES_PER_SHADED = 192        # + 6 x 8 taps x 4 B central differences  
 BYTES_PER_PIXEL = 16          # fp32 RGBA framebuffer store
 DEPTH = 3                     # frames in flight in the N>1 loop (exchange slots; on the GPU each slot has its own HIP stream)
+DUMP_BYTES = 60 * 10**6       # --dump-outputs: a larger frame is sampled down to this (the dump stays under 64 MB)
 
 
 def parse():
@@ -76,6 +83,11 @@ def parse():
     ap.add_argument("--variant", type=int, default=0, help="kernelVariant (experiments)")
     ap.add_argument("--tile", type=int, default=64)
     ap.add_argument("--tile-skew", type=int, default=-1, help="tileSkew of the N>1 deal; -1 = tiles.balanced_skew (diagonals), 0 = plain row-major deal")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements (CPU baseline + parity, C2, C5, frames in flight, scaling model, serial exchange)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the frame of the last timed step to DIR/frame.npy (float32; a fixed seeded sample of its pixels "
+                         "when it exceeds 60 MB)")
     ap.add_argument("--cpu-rows", type=int, default=-1, help="rows of the frame the CPU baseline renders; 0 = skip, -1 = auto")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-inr", action="store_true", help="skip the INR (MFMA) side measurement")
@@ -171,6 +183,18 @@ def dry_run(a, world, rank):
     if world > 1:
         dist.destroy_process_group()
     return 0
+
+
+def dump_frame(path, frame):
+    """``--dump-outputs``: the frame as float32 ``path/frame.npy``.  A frame larger than DUMP_BYTES (a 2048^2 C4 frame is 67 MB)
+    is written as a fixed sample of its pixels (seed 0, ascending row-major pixel index; shape pixels x 4)."""
+    os.makedirs(path, exist_ok=True)
+    a = frame.detach().cpu().numpy().astype(np.float32, copy=False)
+    if a.nbytes > DUMP_BYTES:
+        px = a.reshape(-1, a.shape[-1])
+        keep = np.random.default_rng(0).choice(px.shape[0], DUMP_BYTES // px[0].nbytes, replace=False)
+        a = px[np.sort(keep)]
+    np.save(os.path.join(path, "frame.npy"), a)
 
 
 def measured_traffic(key):
@@ -515,6 +539,8 @@ def main():
     a = parse()
     if a.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if a.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if (a.backend == "gloo") != a.dry_run:
         raise SystemExit("--backend gloo and --dry-run go together: the renderer has no CPU path")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -574,8 +600,10 @@ def main():
         """`count` frames back to back; every frame is fully exchanged and de-tiled on rank 0
         before this returns (the caller synchronises).  N = 1: one stream, one frame after the other (the headline number is
         a single frame's time).  N > 1: frame s runs on slot s % DEPTH's stream — its wait for the slot's previous exchange, its
-        march and its gather are ordered on that stream; frames of different slots overlap."""
+        march and its gather are ordered on that stream; frames of different slots overlap.  Returns the last frame (rank 0's
+        assembled frame when grouped; None on the other ranks)."""
         import contextlib
+        frame = local
         for s in range(count):
             slot = s % DEPTH
             with (torch.cuda.stream(slot_streams[slot]) if ex is not None else contextlib.nullcontext()):
@@ -592,7 +620,8 @@ def main():
         if ex is not None:
             for s in range(max(0, count - DEPTH), count):
                 with torch.cuda.stream(slot_streams[s % DEPTH]):
-                    ex.finish(s % DEPTH)
+                    frame = ex.finish(s % DEPTH)
+        return frame
 
     # untimed: sample accounting by the kernel's own counters
     _, st = mrirt.render_brats(params, [grid], out=local, ext=my_ext, stats=True)
@@ -613,7 +642,7 @@ def main():
     t0 = time.perf_counter()
     # HIP events on the launch stream bracket the march kernel alone (roofline);
     # the wall clock brackets the whole K steps incl. every exchange and de-tiling (value)
-    run_frames(a.steps, ev)
+    last_frame = run_frames(a.steps, ev)
     torch.cuda.synchronize()
     if grouped:
         dist.barrier()
@@ -635,11 +664,13 @@ def main():
         kms = [km.clone() for _ in range(world)]
         dist.all_gather(kms, km)
         kernel_ms_all = [float(k[0]) for k in kms]
+    if a.dump_outputs and rank == 0:
+        dump_frame(a.dump_outputs, last_frame)
 
     # untimed, after the clock has stopped: the exchange step by itself (gather of one frame's tiles to rank 0
     # + de-tiling), serialised — what a frame would pay if nothing overlapped it
     exchange = None
-    if grouped:
+    if grouped and a.full:
         reps = 5
         torch.cuda.synchronize(); dist.barrier(); torch.cuda.synchronize()
         t1 = time.perf_counter()
@@ -720,16 +751,18 @@ def main():
             out["per_rank"] = {"live_samples": [int(c[0]) for c in per_rank], "march_kernel_ms": [round(k, 4) for k in kernel_ms_all],
                                "march_kernel_ms_is": f"this rank's wall time per frame of the timed loop ({DEPTH} frames in flight on {DEPTH} streams: "
                                                      "per-launch durations overlap and are not reported)"}
-            out["exchange"] = exchange
-        if world == 1 and not a.force_exchange and not a.no_pipelined:
+            out["exchange"] = exchange                   # null unless --full
+        # the side measurements: --full only, so that a plain run spends its time on the headline
+        side = world == 1 and a.full
+        if side and not a.force_exchange and not a.no_pipelined:
             out["pipelined"] = pipelined_frames(dev, params, grid, ext, live)
-        if world == 1 and not a.no_k1:
+        if side and not a.no_k1:
             out["k1_reference_path"] = k1_reference_path(dev)
-        if world == 1 and not a.no_inr:
+        if side and not a.no_inr:
             out["inr_path"] = inr_path(dev)
-        if world == 1 and not a.no_scaling_model and not a.no_shade and not a.force_exchange:
+        if side and not a.no_scaling_model and not a.no_shade and not a.force_exchange:
             out["scaling_model"] = scaling_model(dev, grid, n, a.march_steps, ext, a.tile, a.alpha)
-        if not a.no_cpu_baseline and a.cpu_rows != 0 and world == 1:
+        if side and not a.no_cpu_baseline and a.cpu_rows != 0:
             out["cpu_baseline"], band = cpu_baseline(params, vol, ext, min(a.cpu_rows, image), image)
             if not grouped:
                 # the frame of the timed configuration, rendered once more (untimed) and held to the oracle's rows

@@ -28,7 +28,7 @@ for tag in ("c3_vga", "c2_mod4", "c2_quad", "c3_256_512px", "c3_256_1024px"):
 json.dump(db, open(os.path.join(root, "gpurun_out", "r04", "traffic.json"), "w"), indent=2)
 PY
 cp $O/traffic.json $REPO/profiles/traffic.json          # (the copy in this box's tree: bench.py below reads it)
-( cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench_default_trace -- python3 $REPO/bench.py > $O/bench_default_under_rocprof.json 2> $O/bench_default_under_rocprof.err ); echo "bench trace done"
+( cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench_default_trace -- python3 $REPO/bench.py --full > $O/bench_default_under_rocprof.json 2> $O/bench_default_under_rocprof.err ); echo "bench trace done"
 python3 - <<'PY'
 import csv, glob, os
 root = os.environ.get("GRAFT_REPO_ROOT", os.getcwd())
@@ -38,7 +38,7 @@ for f in glob.glob(o + "/bench_default_trace/*/*_kernel_stats.csv"):
     with open(o + "/bench_default_kernel_stats.csv", "w") as fh:
         w = csv.DictWriter(fh, fieldnames=rows[0].keys()); w.writeheader(); w.writerows(rows)
 PY
-python3 bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "bench done"
+python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "bench done"
 python3 bench.py --force-exchange --image 2048 --steps 10 --warmup 2 --no-inr --no-k1 --no-cpu-baseline > $O/bench_force_exchange.json 2>/dev/null; echo "bench fe done"
 python3 tools/configs_bench.py > $O/configs_bench.txt 2>/dev/null; echo "configs done"
 python3 tools/c5_bench.py > $O/c5_bench.txt 2>/dev/null
