@@ -292,9 +292,10 @@ int mrirt_render_brats_skip(const MrirtBratsParams* params, const MrirtRenderExt
                             uint64_t* stats_dev, void* stream);
 /* Host-only query, nothing is launched: 1 = mrirt_render_brats_skip with these arguments marches with an empty-radius map
  * (it builds one into skip->mask, or trusts skip->mapReady); 0 = it is the plain launch and never reads or writes
- * skip->mask (window width or gamma <= 0, a negative weight, a layout / modality count / math mode without a skipping
- * kernel, more than 256 macro cells on an axis, a missing summary): a caller that caches maps must not mark such a scratch
- * as holding one.  < 0: the MrirtStatus the render call would return for these arguments.                               */
+ * skip->mask (window width or gamma <= 0, a negative weight, more than 256 macro cells on an axis, a missing summary, or a
+ * launch whose kernel reads no map — e.g. the generic kernel of a VG / QUAD launch with an overlay shown over label grids
+ * of 2^30 elements or more): a caller that caches maps must not mark such a scratch as holding one.  The answer comes
+ * from the same plan as the launch.  < 0: the MrirtStatus the render call would return for these arguments.            */
 int mrirt_brats_skip_applicable(const MrirtBratsParams* params, const MrirtRenderExt* ext, const void* const vol[4],
                                 const void* labels, const void* preds, const MrirtSkip* skip);
 /* Host-only query, nothing is launched: which march kernel family mrirt_render_brats_skip (skip != NULL) / mrirt_render_brats_ex

@@ -203,7 +203,7 @@ struct Stage {
             const uint32_t ix = (uint32_t)roundf(clampf(s.q[0], 0.0f, a.hiLab[0]));
             const uint32_t iy = (uint32_t)roundf(clampf(s.q[1], 0.0f, a.hiLab[1]));
             const uint32_t iz = (uint32_t)roundf(clampf(s.q[2], 0.0f, a.hiLab[2]));
-            const uint32_t off = a.lab.off(ix, iy, iz) << 2;               // sampleLabel, brats_rt.slang:78-83 (label grids < 4 GiB: launch())
+            const uint32_t off = a.lab.off(ix, iy, iz) << 2;               // sampleLabel, brats_rt.slang:78-83 (label grids < 4 GiB: plan_k1())
             const void* dummy = a.vol[a.chan[0]];
             async_load_u32(lb.seg, a.showSeg != 0 ? (const void*)a.labels : dummy, a.showSeg != 0 ? off : 0u);
             async_load_u32(lb.pred, a.showPred != 0 ? (const void*)a.preds : dummy, a.showPred != 0 ? off : 0u);
@@ -266,7 +266,7 @@ struct Stage {
         Cell c0 = s;
         if (SKIP && empty) { c0.ix = 0u; c0.iy = 0u; c0.iz = 0u; }
 #pragma unroll
-        for (int c = 0; c < kSets; ++c) taps[c].template issue<false>(wg.base(a.vol[kMod4 ? 0 : a.chan[c]]), wg.dims(), c0);   // grid (copy) < 4 GiB (launch())
+        for (int c = 0; c < kSets; ++c) taps[c].template issue<false>(wg.base(a.vol[kMod4 ? 0 : a.chan[c]]), wg.dims(), c0);   // grid (copy) < 4 GiB (plan_k1())
         if constexpr (LABELS) fetch_labels(a, s, lb);
     }
     template <bool STRICT, bool GAMMA1>
@@ -388,7 +388,7 @@ __device__ __forceinline__ void march_skip(const K1Args& a, const WaveGrid<LAYOU
 
 // TAG: the same code under a second symbol (kernelVariant bit 15).  bench.py's side measurements — tile shares, frames in flight —
 // launch the kernel it benches at other sizes and overlapped; under the tag a profiler's per-kernel statistics keep them apart
-// from the benched launches.  Instantiated for the benched configuration only (launch_pipe).
+// from the benched launches.  Instantiated for the benched configuration only (pipe_kernel).
 template <bool STRICT, int LAYOUT, bool SHADE, int NCH, bool GAMMA1, bool LABELS, bool SKIP, bool CELLS = false, bool TAG = false>
 __global__ __launch_bounds__(256, (LABELS || SKIP) ? 3 : 4) void brats_march_pipe_kernel(const K1Args a) {
     __shared__ float4 lutShared[LABELS ? 16 : 1];
@@ -601,147 +601,89 @@ __global__ __launch_bounds__(256, 2) void brats_march_roll_kernel(const K1Args a
     finish(a, kind, oidx, r);
 }
 
-// mrirt_brats_kernel_family: when set, the launchers record which kernel family they WOULD launch and launch nothing
-thread_local int* g_family_probe = nullptr;
+// What a K1 launch runs (plan_k1 decides, launch_plan launches): the kernel family and the template arguments of its kernel.
+struct K1Plan {
+    int status;            // MRIRT_OK, or what the render call returns instead of launching (MRIRT_ERR_LAYOUT)
+    int family;            // MrirtKernelFamily; MRIRT_KERNEL_NONE: nothing to launch (a rank that owns no tile)
+    bool strict;           // STRICT: MRIRT_MATH_STRICT
+    uint32_t layout;       // LAYOUT: MRIRT_LAYOUT_* of the intensity grids
+    bool shade;            // SHADE
+    int nch;               // NCH of the pipelined / rolling kernels
+    bool gamma1;           // GAMMA1: STRICT with gamma == 1
+    bool labels;           // LABELS: the kernel carries the label state
+    bool skipping;         // SKIP: the kernel marches with the empty-radius map (K1Args::skipDist)
+    bool cells;            // CELLS: one label-cell gather per sample (MRIRT_LAYOUT_LABCELL)
+    bool tag;              // TAG: the tagged twin (kernelVariant bit 15)
+    bool leap;             // K1Args::leap of a skipping launch
+};
 
+using K1Kernel = void (*)(K1Args);
+
+// STRICT stands in for `true` and !STRICT for `false` where only STRICT plans take a branch: FAST instantiates no kernel it
+// never launches
 template <bool STRICT, int LAYOUT, bool SHADE, int NCH>
-static int launch_roll(const K1Args& a, hipStream_t s) {
-    const dim3 grid(a.map.chunk * kXcds), block(a.map.blockPx == 8 ? 64 : 256);
-    const bool overlays = a.showSeg != 0 || a.showPred != 0;
-    const bool skipKernel = a.skipDist != nullptr && !overlays && (!STRICT || a.gamma == 1.0f);      // (mrirt_render_brats_skip builds the map only then)
-    if (g_family_probe != nullptr) { *g_family_probe = MRIRT_KERNEL_ROLLING | (skipKernel ? MRIRT_KERNEL_SKIPPING : 0); return MRIRT_OK; }
-    if (skipKernel) {
-        hipLaunchKernelGGL((brats_march_roll_kernel<STRICT, LAYOUT, SHADE, NCH, STRICT, false, true>), grid, block, 0, s, a);
-    } else if (STRICT && a.gamma == 1.0f) {
-        if (overlays) hipLaunchKernelGGL((brats_march_roll_kernel<STRICT, LAYOUT, SHADE, NCH, STRICT, true>), grid, block, 0, s, a);
-        else          hipLaunchKernelGGL((brats_march_roll_kernel<STRICT, LAYOUT, SHADE, NCH, STRICT, false>), grid, block, 0, s, a);
-    } else {
-        hipLaunchKernelGGL((brats_march_roll_kernel<STRICT, LAYOUT, SHADE, NCH, false, true>), grid, block, 0, s, a);
+static K1Kernel pipe_kernel(const K1Plan& pl) {
+    if constexpr (LAYOUT == MRIRT_LAYOUT_QUAD || LAYOUT == MRIRT_LAYOUT_MOD4) {
+        if (pl.cells) return pl.gamma1 ? brats_march_pipe_kernel<STRICT, LAYOUT, SHADE, NCH, STRICT, true, false, true>
+                                       : brats_march_pipe_kernel<STRICT, LAYOUT, SHADE, NCH, false, true, false, true>;
     }
-    MRIRT_HIP(hipGetLastError());
-    return MRIRT_OK;
+    if constexpr (LAYOUT != MRIRT_LAYOUT_LINEAR) {
+        if (pl.skipping) return !pl.gamma1 ? brats_march_pipe_kernel<STRICT, LAYOUT, SHADE, NCH, false, true, !STRICT>
+                              : pl.labels ? brats_march_pipe_kernel<STRICT, LAYOUT, SHADE, NCH, STRICT, true, true>
+                                          : brats_march_pipe_kernel<STRICT, LAYOUT, SHADE, NCH, STRICT, !STRICT, true>;
+    }
+    if constexpr (STRICT && LAYOUT == MRIRT_LAYOUT_VGA && SHADE && NCH == 1) {
+        if (pl.tag) return brats_march_pipe_kernel<STRICT, LAYOUT, SHADE, NCH, STRICT, !STRICT, false, false, true>;
+    }
+    return !pl.gamma1 ? brats_march_pipe_kernel<STRICT, LAYOUT, SHADE, NCH, false, true, false>
+         : pl.labels ? brats_march_pipe_kernel<STRICT, LAYOUT, SHADE, NCH, STRICT, true, false>
+                     : brats_march_pipe_kernel<STRICT, LAYOUT, SHADE, NCH, STRICT, !STRICT, false>;
 }
 
 template <bool STRICT, int LAYOUT, bool SHADE, int NCH>
-static int launch_pipe(const K1Args& a, hipStream_t s) {
-    const dim3 grid(a.map.chunk * kXcds), block(a.map.blockPx == 8 ? 64 : 256);
-    // the fp64 pow only matters for STRICT (FAST's is two instructions): specialise gamma == 1 there
-    // ... and drop the label state when no overlay is shown (STRICT only: FAST already fits)
-    const bool overlays = a.showSeg != 0 || a.showPred != 0;
-    // SKIP exists for the gamma == 1 STRICT kernels and for FAST; any other launch ignores the mask (still exact)
-    // (LINEAR grids have no skipping kernels: mrirt_render_brats_skip never builds a map for them)
-    constexpr bool kHasSkip = LAYOUT != 0;
-    const bool skip = kHasSkip && a.skipDist != nullptr;
-    const bool cellsKernel = (LAYOUT == 3 || LAYOUT == MRIRT_LAYOUT_MOD4) && a.labCell != nullptr && overlays && !skip;      // label cells: the plain pipelined kernel with one label gather
-    const bool skipKernel = skip && (!STRICT || a.gamma == 1.0f);
-    if (g_family_probe != nullptr) {
-        *g_family_probe = MRIRT_KERNEL_PIPELINED | (skipKernel ? MRIRT_KERNEL_SKIPPING : 0) | (cellsKernel ? MRIRT_KERNEL_LABEL_CELLS : 0);
-        return MRIRT_OK;
-    }
-    if constexpr (LAYOUT == 3 || LAYOUT == MRIRT_LAYOUT_MOD4) {
-        if (cellsKernel) {
-            if (STRICT && a.gamma == 1.0f) hipLaunchKernelGGL((brats_march_pipe_kernel<STRICT, LAYOUT, SHADE, NCH, STRICT, true, false, true>), grid, block, 0, s, a);
-            else                           hipLaunchKernelGGL((brats_march_pipe_kernel<STRICT, LAYOUT, SHADE, NCH, false, true, false, true>), grid, block, 0, s, a);
-            MRIRT_HIP(hipGetLastError());
-            return MRIRT_OK;
-        }
-    }
-    if (STRICT && a.gamma == 1.0f && !overlays) {
-        if constexpr (kHasSkip) { if (skip) { hipLaunchKernelGGL((brats_march_pipe_kernel<STRICT, LAYOUT, SHADE, NCH, STRICT, !STRICT, true>), grid, block, 0, s, a); MRIRT_HIP(hipGetLastError()); return MRIRT_OK; } }
-        if constexpr (STRICT && LAYOUT == 4 && SHADE && NCH == 1) {
-            if (a.debugFlags & 256u) {                                  // kernelVariant bit 15: the tagged twin
-                hipLaunchKernelGGL((brats_march_pipe_kernel<STRICT, LAYOUT, SHADE, NCH, STRICT, !STRICT, false, false, true>), grid, block, 0, s, a);
-                MRIRT_HIP(hipGetLastError());
-                return MRIRT_OK;
-            }
-        }
-        hipLaunchKernelGGL((brats_march_pipe_kernel<STRICT, LAYOUT, SHADE, NCH, STRICT, !STRICT, false>), grid, block, 0, s, a);
-    } else if (STRICT && a.gamma == 1.0f) {
-        if constexpr (kHasSkip) { if (skip) { hipLaunchKernelGGL((brats_march_pipe_kernel<STRICT, LAYOUT, SHADE, NCH, STRICT, true, true>), grid, block, 0, s, a); MRIRT_HIP(hipGetLastError()); return MRIRT_OK; } }
-        hipLaunchKernelGGL((brats_march_pipe_kernel<STRICT, LAYOUT, SHADE, NCH, STRICT, true, false>), grid, block, 0, s, a);
-    } else if (!STRICT && skip) {
-        if constexpr (kHasSkip) hipLaunchKernelGGL((brats_march_pipe_kernel<STRICT, LAYOUT, SHADE, NCH, false, true, !STRICT>), grid, block, 0, s, a);
-    } else {
-        hipLaunchKernelGGL((brats_march_pipe_kernel<STRICT, LAYOUT, SHADE, NCH, false, true, false>), grid, block, 0, s, a);
-    }
-    MRIRT_HIP(hipGetLastError());
-    return MRIRT_OK;
+static K1Kernel roll_kernel(const K1Plan& pl) {
+    if (pl.skipping) return brats_march_roll_kernel<STRICT, LAYOUT, SHADE, NCH, STRICT, false, true>;   // (STRICT: gamma == 1)
+    return pl.gamma1 ? brats_march_roll_kernel<STRICT, LAYOUT, SHADE, NCH, STRICT, !STRICT>
+                     : brats_march_roll_kernel<STRICT, LAYOUT, SHADE, NCH, false, true>;
 }
 
 template <bool STRICT, int LAYOUT, bool SHADE>
-static int launch(const K1Args& a, bool pipeAsked, hipStream_t s) {
-    // the pipelined kernels address label words with 32-bit byte offsets (Stage::issue_async)
-    const uint64_t labelElems = (uint64_t)((a.grid.X + 3u) & ~3u) * ((a.grid.Y + 3u) & ~3u) * ((a.grid.Z + 1u) & ~1u);
-    const bool pipe = pipeAsked && !((a.showSeg != 0 || a.showPred != 0) && labelElems >= (1ull << 30));
-    if constexpr (LAYOUT == 2) {                      // VG: 8 float4 per modality per stage -> one modality; more: rolling pairs
-        if (pipe && a.nch == 1 && !a.grid.wide) return launch_pipe<STRICT, 2, SHADE, 1>(a, s);
-        if (pipe && !a.grid.wide && a.showSeg == 0 && a.showPred == 0) {   // (with overlays the generic kernel measured faster)
-            switch (a.nch) {
-                case 2: return launch_roll<STRICT, 2, SHADE, 2>(a, s);
-                case 3: return launch_roll<STRICT, 2, SHADE, 3>(a, s);
-                case 4: return launch_roll<STRICT, 2, SHADE, 4>(a, s);
-                default: break;
-            }
-        }
+static K1Kernel layout_kernel(const K1Plan& pl) {
+    if constexpr (LAYOUT == MRIRT_LAYOUT_VG || LAYOUT == MRIRT_LAYOUT_VGA) {
+        if (pl.family == MRIRT_KERNEL_PIPELINED) return pipe_kernel<STRICT, LAYOUT, SHADE, 1>(pl);
+        if (pl.family == MRIRT_KERNEL_ROLLING)
+            return pl.nch == 2 ? roll_kernel<STRICT, LAYOUT, SHADE, 2>(pl) : pl.nch == 3 ? roll_kernel<STRICT, LAYOUT, SHADE, 3>(pl)
+                                                                          : roll_kernel<STRICT, LAYOUT, SHADE, 4>(pl);
     }
-    if constexpr (LAYOUT == 4) {                      // VGA: as VG; every copy is < 4 GiB by construction (prepare())
-        if (pipe && a.nch == 1) return launch_pipe<STRICT, 4, SHADE, 1>(a, s);
-        if (pipe && a.showSeg == 0 && a.showPred == 0) {
-            switch (a.nch) {
-                case 2: return launch_roll<STRICT, 4, SHADE, 2>(a, s);
-                case 3: return launch_roll<STRICT, 4, SHADE, 3>(a, s);
-                case 4: return launch_roll<STRICT, 4, SHADE, 4>(a, s);
-                default: break;
-            }
-        }
+    if constexpr ((LAYOUT == MRIRT_LAYOUT_LINEAR || LAYOUT == MRIRT_LAYOUT_QUAD) && !SHADE) {
+        if (pl.family == MRIRT_KERNEL_PIPELINED)
+            return pl.nch == 1 ? pipe_kernel<STRICT, LAYOUT, SHADE, 1>(pl) : pl.nch == 2 ? pipe_kernel<STRICT, LAYOUT, SHADE, 2>(pl)
+                 : pl.nch == 3 ? pipe_kernel<STRICT, LAYOUT, SHADE, 3>(pl) : pipe_kernel<STRICT, LAYOUT, SHADE, 4>(pl);
     }
-    if constexpr (LAYOUT == 0 && !SHADE) {            // LINEAR (the plain ABI): 4 register pairs per modality per stage -> up to four
-        if (pipe && a.skipDist == nullptr && (uint64_t)a.grid.X * a.grid.Y * a.grid.Z < (1ull << 30)) {    // 32-bit byte offsets
-            switch (a.nch) {
-                case 1: return launch_pipe<STRICT, 0, false, 1>(a, s);
-                case 2: return launch_pipe<STRICT, 0, false, 2>(a, s);
-                case 3: return launch_pipe<STRICT, 0, false, 3>(a, s);
-                case 4: return launch_pipe<STRICT, 0, false, 4>(a, s);
-                default: break;
-            }
-        }
-    }
-    if constexpr (LAYOUT == 3) {                      // QUAD: 2 float4 per modality per stage -> up to four
-        if (pipe && !a.grid.wide) {
-            switch (a.nch) {
-                case 1: return launch_pipe<STRICT, 3, false, 1>(a, s);
-                case 2: return launch_pipe<STRICT, 3, false, 2>(a, s);
-                case 3: return launch_pipe<STRICT, 3, false, 3>(a, s);
-                case 4: return launch_pipe<STRICT, 3, false, 4>(a, s);
-                default: break;
-            }
-        }
-    }
-    if constexpr (LAYOUT == MRIRT_LAYOUT_MOD4) {      // MOD4: the pipelined kernel or nothing (grids < 4 GiB, label grids < 2^30 elements)
-        (void)pipe;
-        const bool labelsFit = !((a.showSeg != 0 || a.showPred != 0) && labelElems >= (1ull << 30));
-        if (!a.grid.wide && labelsFit && a.classStream == nullptr) return launch_pipe<STRICT, MRIRT_LAYOUT_MOD4, false, 4>(a, s);
-        return MRIRT_ERR_LAYOUT;
-    } else {
-        if (g_family_probe != nullptr) { *g_family_probe = MRIRT_KERNEL_GENERIC; return MRIRT_OK; }
-        const dim3 grid(a.map.chunk * kXcds), block(a.map.blockPx == 8 ? 64 : 256);
-        hipLaunchKernelGGL((brats_march_kernel<STRICT, LAYOUT, SHADE>), grid, block, 0, s, a);
-        MRIRT_HIP(hipGetLastError());
-        return MRIRT_OK;
-    }
+    if constexpr (LAYOUT == MRIRT_LAYOUT_MOD4) return pipe_kernel<STRICT, LAYOUT, SHADE, 4>(pl);
+    else return brats_march_kernel<STRICT, LAYOUT, SHADE>;
 }
 
+// the plan's kernel, launched: no decision is made here
 template <bool STRICT>
-static int launch_layout(const K1Args& a, uint32_t layout, bool shade, bool pipe, hipStream_t s) {
-    switch (layout) {
-        case MRIRT_LAYOUT_LINEAR: return shade ? launch<STRICT, 0, true>(a, false, s) : launch<STRICT, 0, false>(a, pipe, s);
-        case MRIRT_LAYOUT_BRICK:  return shade ? launch<STRICT, 1, true>(a, false, s) : launch<STRICT, 1, false>(a, false, s);
-        case MRIRT_LAYOUT_VG:     return shade ? launch<STRICT, 2, true>(a, pipe, s) : launch<STRICT, 2, false>(a, pipe, s);
-        case MRIRT_LAYOUT_QUAD:   return shade ? (int)MRIRT_ERR_LAYOUT : launch<STRICT, 3, false>(a, pipe, s);
-        case MRIRT_LAYOUT_VGA:    return shade ? launch<STRICT, 4, true>(a, pipe, s) : launch<STRICT, 4, false>(a, pipe, s);
-        case MRIRT_LAYOUT_MOD4:   return shade ? (int)MRIRT_ERR_LAYOUT : launch<STRICT, MRIRT_LAYOUT_MOD4, false>(a, pipe, s);
+static int launch_plan(const K1Plan& pl, const K1Args& a, hipStream_t s) {
+    if (pl.status != MRIRT_OK || pl.family == MRIRT_KERNEL_NONE) return pl.status;
+    if (pl.family == MRIRT_KERNEL_SLAB) return launch_slab_march(a, STRICT, pl.shade, s);
+    if (pl.family == MRIRT_KERNEL_RING) return launch_ring_march(a, STRICT, pl.shade, s);
+    K1Kernel k = nullptr;
+    switch (pl.layout) {                                            // (QUAD and MOD4 plans are unshaded)
+        case MRIRT_LAYOUT_LINEAR: k = pl.shade ? layout_kernel<STRICT, 0, true>(pl) : layout_kernel<STRICT, 0, false>(pl); break;
+        case MRIRT_LAYOUT_BRICK:  k = pl.shade ? layout_kernel<STRICT, 1, true>(pl) : layout_kernel<STRICT, 1, false>(pl); break;
+        case MRIRT_LAYOUT_VG:     k = pl.shade ? layout_kernel<STRICT, 2, true>(pl) : layout_kernel<STRICT, 2, false>(pl); break;
+        case MRIRT_LAYOUT_QUAD:   k = layout_kernel<STRICT, 3, false>(pl); break;
+        case MRIRT_LAYOUT_VGA:    k = pl.shade ? layout_kernel<STRICT, 4, true>(pl) : layout_kernel<STRICT, 4, false>(pl); break;
+        case MRIRT_LAYOUT_MOD4:   k = layout_kernel<STRICT, MRIRT_LAYOUT_MOD4, false>(pl); break;
         default: return MRIRT_ERR_LAYOUT;
     }
+    const dim3 grid(a.map.chunk * kXcds), block(a.map.blockPx == 8 ? 64 : 256);
+    void* args[] = { const_cast<K1Args*>(&a) };
+    MRIRT_HIP(hipLaunchKernel(reinterpret_cast<const void*>(k), grid, block, args, 0, s));
+    return MRIRT_OK;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1043,7 +985,25 @@ __global__ __launch_bounds__(256) void c5_composite_kernel(const K1Args a, C5Ray
     finish(a, kind, oidx, r);      // the frame so far (complete after the last pass); live-sample counters
 }
 
-struct Prepared { uint32_t layout, math; bool shade, pipe, slab, ring; };
+// kernelVariant (MrirtRenderExt): experiments, 0 = library default; every bit is decoded here, into K1Args::map, Prepared and
+// K1Args::debugFlags (bits 7-10 -> debugFlags bits 0-3, bit 12 -> debugFlags bit 5, read by the kernels / brats_ring.hip)
+//   bit 0: row-major instead of Morton lane order
+//   bit 1: flip the choice of 64- / 256-thread workgroups (256 is the default on big VGA launches)
+//   bit 2: no software pipelining (the generic kernel; no skipping)
+//   bit 3: one contiguous run of workgroups per XCD instead of bands
+//   bits 4-5: XCD band height: 0 = one workgroup row, 1 / 2 / 3 = 16 / 32 / 64 px
+//   bit 6: the LDS-staged kernel of brats_slab.hip (VGA, one modality, no overlays, 64-thread workgroups)
+//   bit 7: diagnostic counts in stats[1]: the slab kernel's LDS-served samples; the skipping kernels' samples NOT fetched
+//          (flagged or leapt); the ring kernel's reads outside a window / samples not served by the ring
+//   bit 8: skipping one step at a time (Prepared::leap false: no leaps); the slab kernel counts ring misses, the ring
+//          kernel makes no plane fills (timing only)
+//   bit 9: every band of an XCD starts at x = 0 (no per-band shift of the workgroup order: PixelMap::bandShift); the ring
+//          kernel counts idle lane-rounds in stats[1]
+//   bit 10: the ring kernel: every wave takes the gather march
+//   bit 11: the plane-synchronous LDS ring kernel of brats_ring.hip (the slab kernel's launches; bit 6 wins)
+//   bit 12: the ring kernel: three planes instead of four
+//   bit 15: the tagged twin of the benched kernel (same code, another symbol: bench.py's side measurements)
+struct Prepared { uint32_t layout, math; bool shade, pipe, slab, ring, leap, tag; };
 
 // validate + fill the kernel arguments shared by every K1 entry point
 static int prepare(const MrirtBratsParams* p, const MrirtRenderExt* ext, const void* const vol[4],
@@ -1168,18 +1128,85 @@ static int prepare(const MrirtBratsParams* p, const MrirtRenderExt* ext, const v
     a.expSmall = (fabsf(p->intensityAlpha * p->stepSize) <= 0.125f) ? 1u : 0u;   // val is in [0, 1]
     a.out = nullptr; a.stats = nullptr;
     a.debugFlags = (variant >> 7) & 15u;
-    if (variant & 32768u) a.debugFlags |= 256u;                        // the tagged twin of the benched kernel (launch_pipe)
     if (variant & 4096u) a.debugFlags |= 32u;                          // ring kernel: three planes instead of four
     cfg.layout = layout; cfg.math = math;
     cfg.shade = ext && ext->shadeMode != 0;
     cfg.pipe = a.nch >= 1 && !(variant & 4u);
-    // the LDS-staged kernel (brats_slab.hip): VGA grids, one modality, no overlays, one packet per workgroup; variant bit 6
+    // the LDS-staged kernel (brats_slab.hip): VGA grids, one modality, no overlays, one packet per workgroup
     cfg.slab = layout == MRIRT_LAYOUT_VGA && (variant & 64u) != 0 && cfg.pipe && a.nch == 1 && p->showSeg == 0 && p->showPred == 0 &&
                a.map.blockPx == 8;
-    // the plane-synchronous LDS ring kernel (brats_ring.hip): the same launches; variant bit 11
+    // the plane-synchronous LDS ring kernel (brats_ring.hip): the same launches
     cfg.ring = layout == MRIRT_LAYOUT_VGA && (variant & 2048u) != 0 && (variant & 64u) == 0 && cfg.pipe && a.nch == 1 && p->showSeg == 0 &&
                p->showPred == 0 && a.map.blockPx == 8 && p->dims[0] >= 16 && p->dims[1] >= 16 && p->dims[2] >= 16;
+    cfg.leap = (variant & 256u) == 0u;
+    cfg.tag = (variant & 32768u) != 0u;
     return MRIRT_OK;
+}
+
+// What a K1 launch may be offered for exact empty-space skipping
+enum class SkipOffer {
+    None,      // no MrirtSkip (mrirt_render_brats_ex): the only calls that take the LDS kernels, which have no skipping twin
+    NoMap,     // a MrirtSkip that cannot serve this launch (skip_sound, or no scratch)
+    Map,       // an empty-radius map, if the launch has a kernel that reads one
+};
+
+// Which kernel a K1 launch runs (pure: no side effects, no HIP call).
+static K1Plan plan_k1(const K1Args& a, const Prepared& cfg, SkipOffer offer) {
+    K1Plan pl = {};
+    pl.status = MRIRT_OK;
+    pl.strict = cfg.math == MRIRT_MATH_STRICT;
+    pl.layout = cfg.layout;
+    pl.shade = cfg.shade;
+    pl.nch = (int)a.nch;
+    const bool overlays = a.showSeg != 0 || a.showPred != 0;
+    const bool wide = a.grid.wide != 0;                     // grids >= 4 GiB: 64-bit offsets, the generic kernel
+    // the pipelined kernels address label words with 32-bit byte offsets (Stage::issue_async) and read no class stream
+    // (Stage::issue)
+    const uint64_t labelElems = (uint64_t)((a.grid.X + 3u) & ~3u) * ((a.grid.Y + 3u) & ~3u) * ((a.grid.Z + 1u) & ~1u);
+    const bool labelsFit = !(overlays && labelElems >= (1ull << 30));
+    const bool pipe = cfg.pipe && labelsFit && a.classStream == nullptr;
+    int family = MRIRT_KERNEL_GENERIC;
+    if (offer == SkipOffer::None && (cfg.slab || cfg.ring)) {
+        family = cfg.slab ? MRIRT_KERNEL_SLAB : MRIRT_KERNEL_RING;
+    } else if (cfg.layout == MRIRT_LAYOUT_VG || cfg.layout == MRIRT_LAYOUT_VGA) {
+        // VG: 8 float4 per modality per stage -> one modality pipelined; more: rolling pairs, without overlays (with overlays the
+        // generic kernel measured faster).  VGA: as VG; every copy is < 4 GiB by construction (prepare())
+        const bool fits = pipe && (cfg.layout == MRIRT_LAYOUT_VGA || !wide);
+        if (fits && a.nch == 1) family = MRIRT_KERNEL_PIPELINED;
+        else if (fits && !overlays) family = MRIRT_KERNEL_ROLLING;
+    } else if (cfg.layout == MRIRT_LAYOUT_LINEAR) {
+        // the plain ABI: 4 register pairs per modality per stage -> up to four, unshaded; 32-bit byte offsets
+        if (pipe && !cfg.shade && (uint64_t)a.grid.X * a.grid.Y * a.grid.Z < (1ull << 30)) family = MRIRT_KERNEL_PIPELINED;
+    } else if (cfg.layout == MRIRT_LAYOUT_QUAD) {
+        // 2 float4 per modality per stage -> up to four; no gradients
+        if (cfg.shade) pl.status = MRIRT_ERR_LAYOUT;
+        else if (pipe && !wide) family = MRIRT_KERNEL_PIPELINED;
+    } else if (cfg.layout == MRIRT_LAYOUT_MOD4) {
+        // the pipelined kernel over all four modalities or nothing (grids < 4 GiB, label grids < 2^30 elements, no gradients)
+        if (cfg.shade || wide || !labelsFit || a.classStream != nullptr) pl.status = MRIRT_ERR_LAYOUT;
+        else family = MRIRT_KERNEL_PIPELINED;
+        pl.nch = 4;
+    }
+    if (pl.status != MRIRT_OK) {
+        if (a.map.numBlocks == 0) pl.status = MRIRT_OK;     // (a rank that owns no tile launches nothing: nothing to refuse)
+        return pl;
+    }
+    // the fp64 pow only matters for STRICT (FAST's is two instructions): specialise gamma == 1 there
+    pl.gamma1 = pl.strict && a.gamma == 1.0f;
+    // SKIP: the pipelined kernels of the float4 layouts and the rolling kernel, for gamma == 1 STRICT and for FAST; a map is
+    // used only where the variant asks for the pipelined march (bit 2) and for no LDS kernel
+    const bool skipKernel = (family == MRIRT_KERNEL_PIPELINED && cfg.layout != MRIRT_LAYOUT_LINEAR) || family == MRIRT_KERNEL_ROLLING;
+    pl.skipping = offer == SkipOffer::Map && cfg.pipe && !cfg.slab && !cfg.ring && skipKernel && (!pl.strict || a.gamma == 1.0f);
+    pl.leap = pl.skipping && cfg.leap;
+    // label cells: the plain pipelined kernel with one label gather
+    pl.cells = family == MRIRT_KERNEL_PIPELINED && a.labCell != nullptr && overlays && !pl.skipping;
+    // the label state is dropped where no overlay is shown: STRICT gamma == 1 only (FAST already fits), and in the skipping
+    // rolling kernel, which draws no overlays
+    pl.labels = (overlays || !pl.gamma1) && !(family == MRIRT_KERNEL_ROLLING && pl.skipping);
+    pl.tag = cfg.tag && family == MRIRT_KERNEL_PIPELINED && cfg.layout == MRIRT_LAYOUT_VGA && cfg.shade && a.nch == 1 &&
+             pl.gamma1 && !pl.labels && !pl.skipping;
+    pl.family = a.map.numBlocks == 0 ? (int)MRIRT_KERNEL_NONE : family;   // (a rank that owns no tile launches nothing)
+    return pl;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1258,55 +1285,32 @@ __global__ __launch_bounds__(256) void skip_dist_kernel(const uint32_t* __restri
 
 using namespace mrirt;
 
-// kernelVariant toggles (experiments; 0 = library default):
-//   bit 0: row-major instead of Morton lane order      bit 1: flip 64- / 256-thread workgroups (256 is the default on VGA)
-//   bit 2: no software pipelining                      bits 3-5: XCD band height (prepare(); bits 4-5 = 1: 16 px)
-//   bit 6: the LDS-staged kernel of brats_slab.hip     bit 7: ... counts its LDS-served samples in stats[1]; the skipping
-//                                                             kernels: the samples they did NOT fetch (flagged or leapt)
-//   bit 8: skipping one step at a time (no leaps); in the slab kernel: count ring misses
-//   bit 9: every band of an XCD starts at x = 0 (no per-band shift of the workgroup order: PixelMap::bandShift)
-//   bit 15: the tagged twin of the benched kernel (same code, another symbol: bench.py's side measurements)
-extern "C" int mrirt_render_brats_ex(const MrirtBratsParams* p, const MrirtRenderExt* ext,
-                                     const void* const vol[4], const void* labels, const void* preds,
-                                     void* out_rgba, int64_t pitch_px, uint64_t* stats_dev, void* stream) {
-    if (!out_rgba) return MRIRT_ERR_NULL;
-    K1Args a;
-    Prepared cfg;
-    int rc = prepare(p, ext, vol, labels, preds, true, pitch_px, a, cfg);
-    if (rc != MRIRT_OK) return rc;
-    if (p->showPred != 0 && !preds && a.labCell == nullptr) return MRIRT_ERR_NULL;
-    a.out = out_rgba;
-    a.stats = stats_dev;
-    if (a.map.numBlocks == 0) return MRIRT_OK;   // a rank that owns no tile
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (g_family_probe != nullptr && (cfg.slab || cfg.ring)) { *g_family_probe = cfg.slab ? MRIRT_KERNEL_SLAB : MRIRT_KERNEL_RING; return MRIRT_OK; }
-    if (cfg.slab) return launch_slab_march(a, cfg.math == MRIRT_MATH_STRICT, cfg.shade, s);
-    if (cfg.ring) return launch_ring_march(a, cfg.math == MRIRT_MATH_STRICT, cfg.shade, s);
-    return cfg.math == MRIRT_MATH_STRICT ? launch_layout<true>(a, cfg.layout, cfg.shade, cfg.pipe, s)
-                                         : launch_layout<false>(a, cfg.layout, cfg.shade, cfg.pipe, s);
-}
-
-// Does this launch march with an empty-radius map?  Skipping is sound only where "upper bound <= window floor" implies
-// "contributes nothing": positive window width and gamma (pow(0, g) = 0), non-negative weights (monotone sum), a bound for
-// every enabled modality and a label summary for every shown overlay — and it pays only where the launch has a SKIP kernel:
-// on VG / VGA grids the pipelined kernel (one modality) or the rolling kernel (2-4 modalities, no overlays), on QUAD grids
-// the pipelined kernel (launch()); STRICT with gamma == 1, or FAST (launch_pipe() / launch_roll()).  Anything else would pay
-// the four pre-pass launches for a kernel that ignores the map.  Otherwise: the ordinary launch, no map built.
-static bool skip_applicable(const MrirtBratsParams* p, const K1Args& a, const Prepared& cfg, const MrirtSkip* skip) {
-    bool ok = skip != nullptr && p->ww > 0.0f && p->gamma > 0.0f && a.nch >= 1;      // (the scratch itself: the caller's check)
-    const bool wide = a.grid.wide != 0;
-    const bool overlays = p->showSeg != 0 || p->showPred != 0;
-    const bool layoutOk = ((cfg.layout == MRIRT_LAYOUT_VG && !wide) || cfg.layout == MRIRT_LAYOUT_VGA) ? (a.nch == 1 || !overlays)   // pipelined / rolling
-                        : ((cfg.layout == MRIRT_LAYOUT_QUAD || cfg.layout == MRIRT_LAYOUT_MOD4) && !wide && !cfg.shade);
-    const bool mathOk = cfg.math == MRIRT_MATH_FAST || p->gamma == 1.0f;
-    ok = ok && cfg.pipe && !cfg.slab && !cfg.ring && layoutOk && mathOk;
-    for (int k = 0; k < 3; ++k) ok = ok && (p->dims[k] + 7) / 8 <= 256;   // macro coordinates travel through 8-bit wave reductions
+// Can a map serve this launch?  Skipping is sound only where "upper bound <= window floor" implies "contributes nothing":
+// positive window width and gamma (pow(0, g) = 0), non-negative weights (monotone sum), a bound for every enabled modality
+// and a label summary for every shown overlay; macro coordinates travel through 8-bit wave reductions.  Whether the launch
+// has a kernel that reads the map is plan_k1's question.
+static bool skip_sound(const MrirtBratsParams* p, const K1Args& a, const MrirtSkip* skip) {
+    bool ok = p->ww > 0.0f && p->gamma > 0.0f;
+    for (int k = 0; k < 3; ++k) ok = ok && (p->dims[k] + 7) / 8 <= 256;
     for (uint32_t c = 0; c < a.nch && ok; ++c)
         ok = skip->macroUb[a.chan[c]] != nullptr && a.weight[a.chan[c]] >= 0.0f;
     if (p->showSeg != 0 && !skip->macroSeg) ok = false;
     if (p->showPred != 0 && !skip->macroPred) ok = false;
-    // the label overlays of a launch that takes the generic kernel (label grids >= 2^30 elements: launch()) are not skipped
     return ok;
+}
+
+// prepare() + plan_k1() of mrirt_render_brats_ex / _skip, with every check they make before launching anything
+static int plan_render(const MrirtBratsParams* p, const MrirtRenderExt* ext, const void* const vol[4], const void* labels,
+                       const void* preds, const MrirtSkip* skip, int64_t pitch_px, K1Args& a, K1Plan& pl) {
+    Prepared cfg;
+    const int rc = prepare(p, ext, vol, labels, preds, true, pitch_px, a, cfg);
+    if (rc != MRIRT_OK) return rc;
+    if (p->showPred != 0 && !preds && a.labCell == nullptr) return MRIRT_ERR_NULL;
+    const SkipOffer offer = skip == nullptr ? SkipOffer::None
+                          : skip_sound(p, a, skip) && skip->mask != nullptr ? SkipOffer::Map : SkipOffer::NoMap;
+    pl = plan_k1(a, cfg, offer);
+    if (pl.skipping && (int64_t)skip->maskWords < mrirt_skip_mask_words(p->dims)) return MRIRT_ERR_ARG;
+    return pl.status;
 }
 
 extern "C" int mrirt_render_brats_skip(const MrirtBratsParams* p, const MrirtRenderExt* ext,
@@ -1314,53 +1318,47 @@ extern "C" int mrirt_render_brats_skip(const MrirtBratsParams* p, const MrirtRen
                                        const MrirtSkip* skip, void* out_rgba, int64_t pitch_px,
                                        uint64_t* stats_dev, void* stream) {
     if (!out_rgba) return MRIRT_ERR_NULL;
-    if (!skip) return mrirt_render_brats_ex(p, ext, vol, labels, preds, out_rgba, pitch_px, stats_dev, stream);
     K1Args a;
-    Prepared cfg;
-    int rc = prepare(p, ext, vol, labels, preds, true, pitch_px, a, cfg);
+    K1Plan pl;
+    const int rc = plan_render(p, ext, vol, labels, preds, skip, pitch_px, a, pl);
     if (rc != MRIRT_OK) return rc;
-    if (p->showPred != 0 && !preds && a.labCell == nullptr) return MRIRT_ERR_NULL;
     a.out = out_rgba;
     a.stats = stats_dev;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const bool ok = skip_applicable(p, a, cfg, skip) && skip->mask != nullptr;
-    if (ok && (int64_t)skip->maskWords < mrirt_skip_mask_words(p->dims)) return MRIRT_ERR_ARG;
     // (a rank that owns no tile still builds the map: "this call returned MRIRT_OK" must mean "skip->mask holds the map",
     // which is what a caller's mapReady on the next frame rests on)
-    if (ok && skip->mapReady != 0) {
-        // the scratch already holds this configuration's map (the caller vouches for it: MrirtSkip::mapReady)
+    if (pl.skipping) {
         const uint32_t mx = (p->dims[0] + 7) / 8, my = (p->dims[1] + 7) / 8, mz = (p->dims[2] + 7) / 8, cells = mx * my * mz;
-        a.skipDist = reinterpret_cast<uint8_t*>(skip->mask + skip_bit_words(cells));
-        a.mX = mx; a.mXY = mx * my; a.mY = my; a.mZ = mz;
-        a.leap = (a.debugFlags & 2u) == 0u ? 1u : 0u;
-    } else if (ok && g_family_probe != nullptr) {
-        a.skipDist = reinterpret_cast<uint8_t*>(skip->mask);          // (probe: the launchers only test it against NULL)
-    } else if (ok) {
-        SkipArgs k;
-        const uint32_t mx = (p->dims[0] + 7) / 8, my = (p->dims[1] + 7) / 8, mz = (p->dims[2] + 7) / 8;
-        k.cells = mx * my * mz; k.nch = a.nch;
-        for (uint32_t c = 0; c < 4; ++c) { k.ub[c] = c < a.nch ? skip->macroUb[a.chan[c]] : nullptr; k.w[c] = c < a.nch ? a.weight[a.chan[c]] : 0.0f; }
-        k.wsum = a.wsum; k.tfLo = a.tfLo;
-        k.seg = p->showSeg != 0 ? skip->macroSeg : nullptr;
-        k.pred = p->showPred != 0 ? skip->macroPred : nullptr;
-        k.mask = skip->mask;
-        const dim3 grid((k.cells + 255) / 256), block(256);
-        if (cfg.math == MRIRT_MATH_STRICT) hipLaunchKernelGGL(skip_mask_kernel<true>, grid, block, 0, s, k);
-        else                               hipLaunchKernelGGL(skip_mask_kernel<false>, grid, block, 0, s, k);
-        MRIRT_HIP(hipGetLastError());
         // bits -> distance bytes; the two byte maps follow the bit words in the same scratch (mrirt_skip_mask_words)
-        uint8_t* mapA = reinterpret_cast<uint8_t*>(skip->mask + skip_bit_words(k.cells));
-        uint8_t* mapB = mapA + skip_map_stride(k.cells);
-        hipLaunchKernelGGL(skip_dist_kernel<0>, grid, block, 0, s, skip->mask, (const uint8_t*)nullptr, mapA, mx, my, mz);
-        hipLaunchKernelGGL(skip_dist_kernel<1>, grid, block, 0, s, skip->mask, (const uint8_t*)mapA, mapB, mx, my, mz);
-        hipLaunchKernelGGL(skip_dist_kernel<2>, grid, block, 0, s, skip->mask, (const uint8_t*)mapB, mapA, mx, my, mz);
-        MRIRT_HIP(hipGetLastError());
+        uint8_t* mapA = reinterpret_cast<uint8_t*>(skip->mask + skip_bit_words(cells));
+        if (skip->mapReady == 0) {       // (otherwise the scratch already holds this configuration's map: the caller vouches for it)
+            SkipArgs k;
+            k.cells = cells; k.nch = a.nch;
+            for (uint32_t c = 0; c < 4; ++c) { k.ub[c] = c < a.nch ? skip->macroUb[a.chan[c]] : nullptr; k.w[c] = c < a.nch ? a.weight[a.chan[c]] : 0.0f; }
+            k.wsum = a.wsum; k.tfLo = a.tfLo;
+            k.seg = p->showSeg != 0 ? skip->macroSeg : nullptr;
+            k.pred = p->showPred != 0 ? skip->macroPred : nullptr;
+            k.mask = skip->mask;
+            const dim3 grid((k.cells + 255) / 256), block(256);
+            if (pl.strict) hipLaunchKernelGGL(skip_mask_kernel<true>, grid, block, 0, s, k);
+            else           hipLaunchKernelGGL(skip_mask_kernel<false>, grid, block, 0, s, k);
+            MRIRT_HIP(hipGetLastError());
+            uint8_t* mapB = mapA + skip_map_stride(k.cells);
+            hipLaunchKernelGGL(skip_dist_kernel<0>, grid, block, 0, s, skip->mask, (const uint8_t*)nullptr, mapA, mx, my, mz);
+            hipLaunchKernelGGL(skip_dist_kernel<1>, grid, block, 0, s, skip->mask, (const uint8_t*)mapA, mapB, mx, my, mz);
+            hipLaunchKernelGGL(skip_dist_kernel<2>, grid, block, 0, s, skip->mask, (const uint8_t*)mapB, mapA, mx, my, mz);
+            MRIRT_HIP(hipGetLastError());
+        }
         a.skipDist = mapA; a.mX = mx; a.mXY = mx * my; a.mY = my; a.mZ = mz;
-        a.leap = (a.debugFlags & 2u) == 0u ? 1u : 0u;                 // kernelVariant bit 8: first level only (A/B timing)
+        a.leap = pl.leap ? 1u : 0u;
     }
-    if (a.map.numBlocks == 0) return MRIRT_OK;
-    return cfg.math == MRIRT_MATH_STRICT ? launch_layout<true>(a, cfg.layout, cfg.shade, cfg.pipe, s)
-                                         : launch_layout<false>(a, cfg.layout, cfg.shade, cfg.pipe, s);
+    return pl.strict ? launch_plan<true>(pl, a, s) : launch_plan<false>(pl, a, s);
+}
+
+extern "C" int mrirt_render_brats_ex(const MrirtBratsParams* p, const MrirtRenderExt* ext,
+                                     const void* const vol[4], const void* labels, const void* preds,
+                                     void* out_rgba, int64_t pitch_px, uint64_t* stats_dev, void* stream) {
+    return mrirt_render_brats_skip(p, ext, vol, labels, preds, nullptr, out_rgba, pitch_px, stats_dev, stream);
 }
 
 // 1: mrirt_render_brats_skip with these arguments builds (or reuses) an empty-radius map and marches with it; 0: it is the
@@ -1372,19 +1370,19 @@ extern "C" int mrirt_brats_skip_applicable(const MrirtBratsParams* p, const Mrir
     Prepared cfg;
     const int rc = prepare(p, ext, vol, labels, preds, true, p ? (int64_t)p->imageSize[0] : 0, a, cfg);
     if (rc != MRIRT_OK) return rc;
-    return skip_applicable(p, a, cfg, skip) ? 1 : 0;
+    return skip_sound(p, a, skip) && plan_k1(a, cfg, SkipOffer::Map).skipping ? 1 : 0;
 }
 
 // Which kernel family the render call with these arguments launches (host-only, nothing is launched): MrirtKernelFamily,
 // possibly with MRIRT_KERNEL_SKIPPING / MRIRT_KERNEL_LABEL_CELLS or'ed in; < 0: the status the render call would return.
 extern "C" int mrirt_brats_kernel_family(const MrirtBratsParams* p, const MrirtRenderExt* ext, const void* const vol[4],
                                          const void* labels, const void* preds, const MrirtSkip* skip) {
-    int family = MRIRT_KERNEL_NONE;
-    g_family_probe = &family;
-    const int64_t pitch = p ? (int64_t)p->imageSize[0] : 0;
-    const int rc = mrirt_render_brats_skip(p, ext, vol, labels, preds, skip, reinterpret_cast<void*>(uintptr_t(16)), pitch, nullptr, nullptr);
-    g_family_probe = nullptr;
-    return rc != MRIRT_OK ? rc : family;
+    K1Args a;
+    K1Plan pl;
+    const int rc = plan_render(p, ext, vol, labels, preds, skip, p ? (int64_t)p->imageSize[0] : 0, a, pl);
+    if (rc != MRIRT_OK) return rc;
+    if (pl.family == MRIRT_KERNEL_NONE) return MRIRT_KERNEL_NONE;
+    return pl.family | (pl.skipping ? MRIRT_KERNEL_SKIPPING : 0) | (pl.cells ? MRIRT_KERNEL_LABEL_CELLS : 0);
 }
 
 extern "C" int mrirt_render_brats(const MrirtBratsParams* params, const float* const vol[4],
@@ -1407,12 +1405,11 @@ extern "C" int mrirt_render_brats_stream(const MrirtBratsParams* p, const MrirtR
     if (rc != MRIRT_OK) return rc;
     if (a.labCell != nullptr) return MRIRT_ERR_LAYOUT;           // (the class stream replaces gPreds; label cells carry both grids)
     if (p->showPred == 0) return MRIRT_ERR_ARG;
-    a.classStream = classes; a.rayOffsets = offsets;
+    a.classStream = classes; a.rayOffsets = offsets;             // (plan_k1: the generic kernel, which reads the stream)
     a.out = out_rgba; a.stats = stats_dev;
+    const K1Plan pl = plan_k1(a, cfg, SkipOffer::None);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    // the generic kernel: the pipelined ones do not read a class stream (Stage::issue)
-    return cfg.math == MRIRT_MATH_STRICT ? launch_layout<true>(a, cfg.layout, cfg.shade, false, s)
-                                         : launch_layout<false>(a, cfg.layout, cfg.shade, false, s);
+    return pl.strict ? launch_plan<true>(pl, a, s) : launch_plan<false>(pl, a, s);
 }
 
 extern "C" int mrirt_brats_sample_counts(const MrirtBratsParams* p, const MrirtRenderExt* ext, uint32_t* counts, void* stream) {

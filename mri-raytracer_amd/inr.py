@@ -304,7 +304,7 @@ def render_brats_inr(params, intensities, net: PackedMLP, zmu, zsigma, labels=No
     if net.desc.kind not in (KIND_FOURIER_RELU, KIND_SIREN) or net.desc.numMods != 4:
         raise ValueError("render_brats_inr needs a Fourier/ReLU or SIREN network over 4 modalities "
                          "(pack_mlp(params, KIND_FOURIER_RELU, K, 4) / pack_mlp(params, KIND_SIREN, 0, 4))")
-    P, E, vols, lab, _ = _bind_brats(params, intensities, labels, None, ext, dev, pred_stream=True)
+    P, E, vols, lab, _, _ = _bind_brats(params, intensities, labels, None, ext, dev, pred_stream=True)
     if any(v is None for v in vols):
         raise ValueError("the MLP reads all four modalities: bind gIntensity0..3")
     if E.tileSize > 0:

@@ -257,7 +257,7 @@ def _alloc_out(params_w: int, params_h: int, ext: _lib.RenderExt, dev, out):
 
 
 def _bind_brats(params, intensities, labels, preds, ext, dev, pred_stream: bool = False):
-    """gParams dict + bound grids -> (MrirtBratsParams, MrirtRenderExt, device tensors), with the
+    """gParams dict + bound grids -> (MrirtBratsParams, MrirtRenderExt, device tensors, the four bound intensities), with the
     layout / size checks every K1 entry point shares."""
     P = brats_params(params)
     e = dict(ext or {})
@@ -303,7 +303,7 @@ def _bind_brats(params, intensities, labels, preds, ext, dev, pred_stream: bool 
         prd = None
     elif P.showPred != 0 and not pred_stream and (prd is None or prd.numel() < need[lab_lay]):
         raise ValueError("showPred is set but gPreds is missing or too small")
-    return P, E, vols, lab, prd
+    return P, E, vols, lab, prd, intensities
 
 
 KERNEL_FAMILIES = {0: "none", 1: "generic", 2: "pipelined", 3: "rolling", 4: "slab", 5: "ring"}
@@ -363,8 +363,9 @@ _SKIP_MAPS_MAX = 8
 
 def _bind_skip(P, E, vp, lab, prd, intensities, labels, preds, dev, stream):
     """MrirtSkip for one call, or (None, None, None) when this launch has no use for a map (it then goes out as the plain
-    render call and no scratch exists).  Returns (S, entry, hold): ``hold`` keeps every tensor S points at alive until the
-    caller drops it — after the launch has been enqueued, at the end of ``render_brats``.
+    render call and no scratch exists).  ``intensities``: the four bound grids as ``_bind_brats`` returns them.  Returns
+    (S, entry, hold): ``hold`` keeps every tensor S points at alive until the caller drops it — after the launch has been
+    enqueued, at the end of ``render_brats``.
 
     The map depends on the grids' summaries and on (dims, ww, wl, gamma, volEnabled, volWeight, showSeg, showPred, math) —
     not on the camera, and not on the layout / shading / kernel variant, which only decide WHETHER a launch marches with a
@@ -379,7 +380,7 @@ def _bind_skip(P, E, vp, lab, prd, intensities, labels, preds, dev, stream):
     for m in range(4):
         g = intensities[m] if m < len(intensities) else None
         if P.volEnabled[m] != 0:
-            mac = (g.macros[m] if g.macros is not None else None) if isinstance(g, Grid) and g.layout == "mod4" else getattr(g, "macro", None)
+            mac = g.macros[m] if getattr(g, "macros", None) is not None else getattr(g, "macro", None)
             if not isinstance(g, Grid) or mac is None or mac.dtype != torch.float32:
                 raise ValueError(f"skip=True: gIntensity{m} must be a Grid made by upload_grid / upload_mod4 (it carries the macro-cell bounds)")
             S.macroUb[m] = mac.data_ptr()
@@ -452,7 +453,7 @@ def render_brats(params: Mapping[str, Any], intensities: Sequence[Optional[Union
     # the launch stream, so the kernels are ordered after their producers and the caching allocator ties the
     # memory to that stream
     with _on_stream(stream):
-        P, E, vols, lab, prd = _bind_brats(params, intensities, labels, preds, ext, dev)
+        P, E, vols, lab, prd, intensities = _bind_brats(params, intensities, labels, preds, ext, dev)
         o, pitch = _alloc_out(int(P.imageSize[0]), int(P.imageSize[1]), E, dev, out)
         vp = (C.c_void_p * 4)(*[C.c_void_p(t.data_ptr()) if t is not None else None for t in vols])
         st = torch.zeros(2, dtype=torch.int64, device=dev) if stats else None

@@ -52,7 +52,7 @@ def test_wide_vg_grid_takes_the_generic_kernel_and_matches_the_oracle():
 
 def test_label_and_linear_grids_of_2_to_the_30_elements():
     """1024^3: the label grid has 2^30 words and the LINEAR intensity grid 2^30 voxels — both past what the pipelined kernels'
-    32-bit byte offsets reach (launch()): generic kernel, oracle bits, incl. the last voxel of both grids."""
+    32-bit byte offsets reach (plan_k1()): generic kernel, oracle bits, incl. the last voxel of both grids."""
     import mrirt
     from mrirt import render, synth
     from oracle import oracle_c

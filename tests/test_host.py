@@ -323,6 +323,16 @@ def test_kernel_family_choices_incl_the_4gib_fallbacks():
     assert fam(dict(c2, volEnabled=(0, 0, 0, 0)), dict(layout="mod4"))["family"] == "pipelined"
     four = synth.brats_scene(256, 512, 256, channels=4)
     assert fam(four, dict(synth.SHADE_EXT, layout="vga"))["family"] == "rolling"
+    assert fam(four, dict(synth.SHADE_EXT, layout="vga"), skip=True) == {"family": "rolling", "skipping": True, "label_cells": False}
+    # FAST skips whatever gamma is; STRICT only at gamma == 1 (the skipping kernels specialise it)
+    g08 = dict(c3, gamma=0.8)
+    assert fam(g08, dict(synth.SHADE_EXT, layout="vg", math="fast"), skip=True) == {"family": "pipelined", "skipping": True, "label_cells": False}
+    assert fam(g08, dict(synth.SHADE_EXT, layout="vg"), skip=True) == {"family": "pipelined", "skipping": False, "label_cells": False}
+    assert fam(c2, dict(layout="quad", labelLayout="labcell", math="fast")) == {"family": "pipelined", "skipping": False, "label_cells": True}
+    # a tile rank that owns no tile launches nothing
+    tiles = synth.brats_scene(64, 64, 64, channels=1)
+    assert fam(tiles, dict(layout="vg", tileSize=64, tileRank=1, tileWorld=2))["family"] == "none"
+    assert fam(tiles, dict(layout="vg", tileSize=64, tileRank=0, tileWorld=2))["family"] == "pipelined"
     assert fam(dict(four, showSeg=1), dict(synth.SHADE_EXT, layout="vga"))["family"] == "generic"      # overlays: the generic kernel measured faster
     # ---- beyond 32-bit byte offsets ----
     wide = synth.brats_scene(0, 256, 200, dims=(1024, 1024, 272), channels=1)
@@ -332,7 +342,12 @@ def test_kernel_family_choices_incl_the_4gib_fallbacks():
     assert fam(synth.brats_scene(644, 256, 200, channels=1), dict(layout="quad"))["family"] == "pipelined"     # 3.98 GiB: still 32-bit
     big = synth.brats_scene(1024, 128, 200, channels=1, show_seg=True)
     assert fam(big, dict(layout="linear"))["family"] == "generic"                  # 2^30 voxels, 2^30 label words
-    assert fam(synth.brats_scene(0, 128, 200, dims=(1024, 1024, 1020), channels=1, show_seg=True), dict(layout="quad", labelLayout="brick"))["family"] == "generic"
+    huge_labels = synth.brats_scene(0, 128, 200, dims=(1024, 1024, 1020), channels=1, show_seg=True)
+    assert fam(huge_labels, dict(layout="quad", labelLayout="brick"))["family"] == "generic"
+    # ... so no map is built for them either: mrirt_brats_skip_applicable asks the launch's own plan
+    for layout in ("quad", "vg"):
+        assert _skip_applicable(huge_labels, dict(layout=layout, labelLayout="brick")) == 0
+    assert _skip_applicable(c2, dict(layout="quad", labelLayout="brick")) == 1
     # VGA copies past 2^28 elements are refused outright (32-bit byte offsets inside a copy): an error, not a fault
     import pytest as _pt
     with _pt.raises(_lib_error()):
@@ -342,6 +357,18 @@ def test_kernel_family_choices_incl_the_4gib_fallbacks():
         fam(c2, dict(synth.SHADE_EXT, layout="mod4"))
     with _pt.raises(_lib_error()):
         fam(synth.brats_scene(0, 64, 64, dims=(1024, 1024, 272), channels=4), dict(layout="mod4"))
+
+
+def _skip_applicable(p, ext):
+    """mrirt_brats_skip_applicable with every summary offered, placeholder addresses for the grids (as render.kernel_family)."""
+    P, E = params.brats_params(p), params.render_ext(ext)
+    fake = C.c_void_p(0x1000)
+    vp = (C.c_void_p * 4)(*[fake if P.volEnabled[m] != 0 else None for m in range(4)])
+    S = _lib.Skip()
+    for m in range(4):
+        S.macroUb[m] = 0x1000 if P.volEnabled[m] != 0 else None
+    S.macroSeg = S.macroPred = 0x1000
+    return int(_lib.lib().mrirt_brats_skip_applicable(C.byref(P), C.byref(E), vp, fake, fake, C.byref(S)))
 
 
 def _lib_error():
