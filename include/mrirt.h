@@ -28,6 +28,8 @@ extern "C" {
  *    switches of version 2), mrirt_brats_skip_applicable, mrirt_install_abort_trace. */
 /* 4: MRIRT_LAYOUT_MOD4 + mrirt_build_mod4_grid (the four modalities of a BraTS case as ONE float4 grid: unshaded K1 and
  *    mrirt_render_brats_inr); the packed INR image ends in 32 KiB of slack more (mrirt_inr_pack_bytes says how much to allocate). */
+/*    Backward-compatible additions under the same version: MrirtMeshParams + mrirt_render_mesh (K4, the triangle-mesh BVH
+ *    ray tracer), mrirt_sizeof(6). */
 #define MRIRT_ABI_VERSION 4
 
 typedef enum MrirtStatus {
@@ -260,6 +262,34 @@ int mrirt_render_sdf(const MrirtSdfParams* params, uint32_t width, uint32_t heig
                      float* out_rgba, int64_t pitch_px, void* stream);
 
 /* ------------------------------------------------------------------------------------ */
+/* K4  compute_main (triangle-mesh BVH ray tracer)                                       */
+/* ------------------------------------------------------------------------------------ */
+
+/* Mirror of `struct Params`, scripts/mesh_rt/mesh_rt.slang:12-21, in cbuffer packing: 80 bytes, eye at 16, U at 32, V at 48,
+ * W at 64 (padEye is the 4-byte hole the packing leaves after eye).  maxBounces is read by nothing, as in the shader. */
+typedef struct MrirtMeshParams {
+    uint32_t imageSize[2]; float fovY; uint32_t maxBounces;
+    float eye[3]; float padEye;
+    float U[3]; float padU; float V[3]; float padV; float W[3]; float padW;
+} MrirtMeshParams;
+
+/* Drop-in for kernel.dispatch(...) of compute_main, scripts/mesh_rt/app.py:233-243: one ray per pixel, the frame in STRICT
+ * math only (bit-identical to the shader's arithmetic, unfused fp32 in its order).
+ *   nodes = gBVHNodes (float4 x 2 per node, bvh.py's packing), tris = gTris (uint4, xyz used), verts = gVerts (float4, xyz)
+ *   maxDepth: nodes on the longest root-to-leaf path (the traversal stack holds at most that many entries), 1..64
+ *   ext (may be NULL): cameraMode, orthoHalfHeight, outFormat; math FAST, tiles or a kernelVariant -> MRIRT_ERR_ARG
+ *   stats_dev (optional): 2 device uint64 counters, atomically incremented by {nodes popped, triangles tested}
+ *   status_dev (optional): device word; bit 0 is set (atomic or) by a ray that met an index out of range, a stack deeper
+ *              than maxDepth or more pops than nodeCount (a cycle).  Such a ray stops and its pixel is (1, 0, 1, 1).
+ * nodeCount / triCount must be in [1, 2^23) (the shader decodes indices stored as floats with int(x + 0.5)), vertCount >= 1. */
+int mrirt_render_mesh(const MrirtMeshParams* params, const MrirtRenderExt* ext,
+                      const float* nodes, uint32_t nodeCount,
+                      const uint32_t* tris, uint32_t triCount,
+                      const float* verts, uint32_t vertCount,
+                      uint32_t maxDepth, void* out_rgba, int64_t pitch_px,
+                      uint64_t* stats_dev, uint32_t* status_dev, void* stream);
+
+/* ------------------------------------------------------------------------------------ */
 /* Tile sharding helpers (multi-GPU)                               */
 /* ------------------------------------------------------------------------------------ */
 /* Exact empty-space skipping (build-defined acceleration).  The frame and the
@@ -406,7 +436,8 @@ int mrirt_render_brats_inr(const MrirtBratsParams* params, const MrirtRenderExt*
 int mrirt_abi_version(void);
 const char* mrirt_status_string(int status);
 int mrirt_last_hip_error(void);            /* hipError_t of the last failed HIP call on this thread */
-uint32_t mrirt_sizeof(uint32_t which);     /* 0 BratsParams, 1 RenderExt, 2 VolumeParams, 3 SdfParams, 4 InrDesc, 5 Skip */
+uint32_t mrirt_sizeof(uint32_t which);     /* 0 BratsParams, 1 RenderExt, 2 VolumeParams, 3 SdfParams, 4 InrDesc, 5 Skip,
+                                              6 MeshParams */
 /* Opt-in diagnostics (host only; the library installs nothing by itself): a SIGABRT handler that writes the native
  * backtrace of the aborting thread and, when file descriptor 2 has been redirected into a regular file (a test runner's
  * capture), the tail of that file to `fd` — a descriptor the caller duplicated before the redirection — and then chains

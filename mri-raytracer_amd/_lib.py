@@ -17,7 +17,7 @@ CSRC = PKG_DIR / "csrc"
 INCLUDE = PKG_DIR.parent / "include"
 SO_PATH = pathlib.Path(os.environ.get("MRIRT_LIB", PKG_DIR / "libmrirt.so"))   # override: A/B builds in development
 HIP_SOURCES = ["brats_march.hip", "brats_slab.hip", "brats_ring.hip", "volume_march.hip", "grid_ops.hip", "inr_mlp.hip",
-               "abort_trace.cpp"]
+               "mesh_rt.hip", "abort_trace.cpp"]
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17", "-Wall"]
 
 # every extern "C" symbol include/mrirt.h declares
@@ -25,7 +25,7 @@ ABI_SYMBOLS = [
     "mrirt_render_brats", "mrirt_render_brats_ex", "mrirt_brats_sample_counts", "mrirt_brats_emit_samples",
     "mrirt_render_brats_stream", "mrirt_brats_inr_scratch_bytes", "mrirt_render_brats_inr", "mrirt_brick_elems", "mrirt_brick_grid",
     "mrirt_unbrick_grid", "mrirt_vec4_elems", "mrirt_vga_elems", "mrirt_build_vec4_grid", "mrirt_build_label_cells", "mrirt_build_mod4_grid", "mrirt_bc4_decode", "mrirt_macro_cells", "mrirt_skip_mask_words",
-    "mrirt_build_macro_max", "mrirt_build_macro_labels", "mrirt_render_brats_skip", "mrirt_render_volume", "mrirt_build_cell8", "mrirt_render_sdf", "mrirt_tiles_for_rank",
+    "mrirt_build_macro_max", "mrirt_build_macro_labels", "mrirt_render_brats_skip", "mrirt_render_volume", "mrirt_build_cell8", "mrirt_render_sdf", "mrirt_render_mesh", "mrirt_tiles_for_rank",
     "mrirt_detile", "mrirt_inr_pack_bytes", "mrirt_inr_pack_weights", "mrirt_inr_calibrate", "mrirt_inr_forward", "mrirt_inr_forward_refined",
     "mrirt_inr_predict_volume", "mrirt_abi_version", "mrirt_status_string", "mrirt_last_hip_error",
     "mrirt_sizeof", "mrirt_brats_skip_applicable", "mrirt_brats_kernel_family", "mrirt_install_abort_trace",
@@ -89,6 +89,15 @@ class SdfParams(C.Structure):
         ("maxDistance", f32), ("hitThreshold", f32), ("normalEps", f32), ("pad0", f32),
         ("gEye", f32 * 3), ("pad1", f32), ("gU", f32 * 3), ("pad2", f32), ("gV", f32 * 3), ("pad3", f32),
         ("gW", f32 * 3), ("pad4", f32),
+    ]
+
+
+class MeshParams(C.Structure):
+    """MrirtMeshParams == struct Params of scripts/mesh_rt/mesh_rt.slang:12-21 (cbuffer packing, 80 bytes)."""
+    _fields_ = [
+        ("imageSize", u32 * 2), ("fovY", f32), ("maxBounces", u32),
+        ("eye", f32 * 3), ("padEye", f32), ("U", f32 * 3), ("padU", f32), ("V", f32 * 3), ("padV", f32),
+        ("W", f32 * 3), ("padW", f32),
     ]
 
 
@@ -284,6 +293,8 @@ def lib() -> C.CDLL:
     l.mrirt_bc4_decode.restype = i32
     l.mrirt_render_volume.argtypes = [C.POINTER(VolumeParams), C.POINTER(RenderExt), vp, u32, vp, i64, vp, vp]
     l.mrirt_render_sdf.argtypes = [C.POINTER(SdfParams), u32, u32, vp, i64, vp]
+    l.mrirt_render_mesh.argtypes = [C.POINTER(MeshParams), C.POINTER(RenderExt), vp, u32, vp, u32, vp, u32, u32, vp, i64, vp, vp, vp]
+    l.mrirt_render_mesh.restype = i32
     l.mrirt_tiles_for_rank.argtypes = [u32, u32, u32, u32, u32]
     l.mrirt_tiles_for_rank.restype = i64
     l.mrirt_detile.argtypes = [vp, vp, u32, u32, i64, u32, u32, u32, u32, vp]
@@ -306,7 +317,7 @@ def lib() -> C.CDLL:
     if l.mrirt_abi_version() != ABI_VERSION:
         raise ImportError(f"ABI mismatch: {SO_PATH} reports version {l.mrirt_abi_version()}, this binding expects {ABI_VERSION} "
                           "(rebuild: python -c \"import __graft_entry__ as g; g.build()\")")
-    for which, st in enumerate((BratsParams, RenderExt, VolumeParams, SdfParams, InrDesc, Skip)):
+    for which, st in enumerate((BratsParams, RenderExt, VolumeParams, SdfParams, InrDesc, Skip, MeshParams)):
         if l.mrirt_sizeof(which) != C.sizeof(st):
             raise ImportError(f"ABI mismatch: {st.__name__} is {C.sizeof(st)} B here, {l.mrirt_sizeof(which)} B in {SO_PATH}")
     _LIB = l

@@ -437,6 +437,7 @@ extern "C" uint32_t mrirt_sizeof(uint32_t which) {
         case 3: return (uint32_t)sizeof(MrirtSdfParams);
         case 4: return (uint32_t)sizeof(MrirtInrDesc);
         case 5: return (uint32_t)sizeof(MrirtSkip);
+        case 6: return (uint32_t)sizeof(MrirtMeshParams);
         default: return 0;
     }
 }

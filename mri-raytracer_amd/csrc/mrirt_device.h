@@ -161,10 +161,10 @@ template <> struct M<false> {
 // result as fminf(fmaxf(NaN, lo), hi) and as HLSL saturate(NaN) = 0 (requires lo <= hi).
 __device__ __forceinline__ float clampf(float x, float lo, float hi) { return __builtin_amdgcn_fmed3f(x, lo, hi); }
 __device__ __forceinline__ float satf(float x) { return __builtin_amdgcn_fmed3f(x, 0.0f, 1.0f); }
-__device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, float by, float bz) {
+MRIRT_HD float dot3(float ax, float ay, float az, float bx, float by, float bz) {
     return (ax * bx + ay * by) + az * bz;
 }
-__device__ __forceinline__ void normalize3(float& x, float& y, float& z) {
+MRIRT_HD void normalize3(float& x, float& y, float& z) {
     float n = sqrtf(dot3(x, y, z, x, y, z));
     x = x / n; y = y / n; z = z / n;
 }

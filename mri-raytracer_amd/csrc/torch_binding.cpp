@@ -5,7 +5,7 @@
 // holding the C structs byte for byte; every size check the C side cannot make (it only sees pointers) is made here.
 // No device code in this file: it is compiled by the host compiler against the torch headers and linked to
 // libmrirt.so, whose kernels do the work.  Replaces kernel.dispatch of inr/viewer/brats_viewer.py:431-442,
-// scripts/volumeRendering/app.py:350-358 and scripts/raymarch/app.py:212-223 for callers that want operators.
+// scripts/volumeRendering/app.py:350-358, scripts/raymarch/app.py:212-223 and scripts/mesh_rt/app.py:233-243 for callers that want operators.
 #include <ATen/ATen.h>
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
@@ -137,6 +137,31 @@ Tensor render_sdf(const Tensor& params, int64_t width, int64_t height, const Ten
     return out;
 }
 
+// compute_main (scripts/mesh_rt/mesh_rt.slang:138-164) through mrirt_render_mesh; the counts are the buffers' sizes
+// (nodes float32 [2N x 4], tris int32 [M x 4], verts float32 [V x 4]), so the kernel's guards keep every read inside them
+Tensor render_mesh(const Tensor& params, const Tensor& ext, const Tensor& nodes, const Tensor& tris, const Tensor& verts,
+                   int64_t max_depth) {
+    const MrirtMeshParams P = unblob<MrirtMeshParams>(params, "MrirtMeshParams");
+    const MrirtRenderExt E = unblob<MrirtRenderExt>(ext, "MrirtRenderExt");
+    const float* n = static_cast<const float*>(dev_ptr(nodes, at::kFloat, "gBVHNodes"));
+    const uint32_t* t = static_cast<const uint32_t*>(dev_ptr(tris, at::kInt, "gTris"));
+    const float* v = static_cast<const float*>(dev_ptr(verts, at::kFloat, "gVerts"));
+    std::optional<at::Device> dev;
+    same_device(dev, nodes, "gBVHNodes");
+    same_device(dev, tris, "gTris");
+    same_device(dev, verts, "gVerts");
+    TORCH_CHECK_VALUE(max_depth >= 0 && max_depth <= 64, "max_depth must be in [0, 64]");
+    DeviceGuard guard(*dev);
+    const auto dt = E.outFormat == MRIRT_OUT_RGBA16F ? at::kHalf : at::kFloat;
+    Tensor out = at::empty({ (int64_t)P.imageSize[1], (int64_t)P.imageSize[0], 4 }, at::TensorOptions().dtype(dt).device(*dev));
+    const int64_t nc = nodes.numel() / 8, tc = tris.numel() / 4, vc = verts.numel() / 4;
+    TORCH_CHECK_VALUE(nc < (1 << 30) && tc < (1 << 30) && vc < (1ll << 32), "buffer too large");
+    check(mrirt_render_mesh(&P, &E, n, (uint32_t)nc, t, (uint32_t)tc, v, (uint32_t)vc, (uint32_t)max_depth, out.data_ptr(),
+                            (int64_t)P.imageSize[0], nullptr, nullptr, current_stream()),
+          "mrirt_render_mesh");
+    return out;
+}
+
 // logits [n, out_dim] of the packed MLP (inr/inr/model.py:21-50 for kind 0, notebooks/neumors_inr.ipynb:1165-1178 for
 // kind 1; kinds 2 / 3 take the [n, in_dim] input matrix in `feats`) through mrirt_inr_forward
 Tensor inr_forward(const Tensor& weights, const Tensor& biases, int64_t kind, int64_t num_layers, int64_t in_dim, int64_t out_dim,
@@ -175,6 +200,7 @@ TORCH_LIBRARY(mrirt_native, m) {
     m.def("render_brats(Tensor params, Tensor ext, Tensor? vol0, Tensor? vol1, Tensor? vol2, Tensor? vol3, Tensor? labels, Tensor? preds) -> Tensor");
     m.def("render_volume(Tensor params, Tensor ext, Tensor volume, int mode) -> Tensor");
     m.def("render_sdf(Tensor params, int width, int height, Tensor like) -> Tensor");
+    m.def("render_mesh(Tensor params, Tensor ext, Tensor nodes, Tensor tris, Tensor verts, int max_depth) -> Tensor");
     m.def("inr_forward(Tensor weights, Tensor biases, int kind, int num_layers, int in_dim, int out_dim, int hidden, "
           "int fourier_freqs, int num_mods, float w0, Tensor? coords, Tensor? feats, int n) -> Tensor");
 }
@@ -185,5 +211,6 @@ TORCH_LIBRARY_IMPL(mrirt_native, CompositeExplicitAutograd, m) {
     m.impl("render_brats", &render_brats);
     m.impl("render_volume", &render_volume);
     m.impl("render_sdf", &render_sdf);
+    m.impl("render_mesh", &render_mesh);
     m.impl("inr_forward", &inr_forward);
 }

@@ -120,3 +120,14 @@ def sdf_params(p: Mapping[str, Any], eye, U, V, W) -> _lib.SdfParams:
     for name, v in (("gEye", eye), ("gU", U), ("gV", V), ("gW", W)):
         _set3(getattr(s, name), v, name)
     return s
+
+
+def mesh_params(p: Mapping[str, Any]) -> _lib.MeshParams:
+    """dict (mesh_rt/app.py:224-232) -> MrirtMeshParams."""
+    s = _lib.MeshParams()
+    s.imageSize[0], s.imageSize[1] = int(p["imageSize"][0]), int(p["imageSize"][1])
+    s.fovY = float(np.float32(p["fovY"]))
+    s.maxBounces = int(p.get("maxBounces", 1))
+    for k in ("eye", "U", "V", "W"):
+        _set3(getattr(s, k), p[k], k)
+    return s

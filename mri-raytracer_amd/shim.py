@@ -4,7 +4,7 @@ The reference's only render interface is the third-party slangpy call
     kernel = device.create_compute_kernel(device.load_program("brats_rt.slang", ["brats_main"]))
     kernel.dispatch(thread_count=[W, H, 1], vars={...}, command_encoder=ce)
 (inr/viewer/brats_viewer.py:85-86,431-442; scripts/volumeRendering/app.py:30-31,350-358;
-scripts/raymarch/app.py:26-27,212-223).  This module offers the same call shape — binding BY
+scripts/raymarch/app.py:26-27,212-223; scripts/mesh_rt/app.py:36-37,213-243).  This module offers the same call shape — binding BY
 NAME to the Slang globals, ``gParams`` as a dict of cbuffer fields, caller-owned buffers and
 output texture — backed by the gfx950 kernels, so viewer-style code swaps ``spy.Device`` for
 ``mrirt.shim.Device`` and nothing else.  Work is enqueued on the current HIP stream and not
@@ -19,6 +19,7 @@ from typing import Any, Dict, List, Mapping, Optional, Sequence, Union
 import numpy as np
 import torch
 
+from . import mesh as _mesh
 from . import render as _r
 
 # entry point -> (kernel id, the Slang globals it binds)
@@ -27,6 +28,7 @@ _ENTRY_POINTS = {
                           "gLabels", "gPreds", "gParams"}),
     "volume_cs": ("K2", {"gOutput", "gParams", "gVolumeU8"}),
     "raymarch_cs": ("K3", {"render_texture", "gParams", "gEye", "gU", "gV", "gW"}),
+    "compute_main": ("K4", {"gOutput", "gBVHNodes", "gTris", "gVerts", "gParams"}),
 }
 
 
@@ -130,6 +132,8 @@ class ComputeKernel:
             self._brats(tc, vars, ext)
         elif self.kind == "K2":
             self._volume(tc, vars, ext)
+        elif self.kind == "K4":
+            self._mesh_rt(tc, vars, ext)
         else:
             self._sdf(tc, vars)
 
@@ -235,6 +239,29 @@ class ComputeKernel:
         t = v.tensor if isinstance(v, Buffer) else v
         _r.render_volume_u8(p, t, mode="u32x4", out=tex.tensor, ext=e)
 
+    def _mesh_rt(self, tc, vars, ext):
+        p, tex = vars["gParams"], vars["gOutput"]
+        e = self._out(tex, tc, ext)
+        e.pop("layout", None)
+        if (int(p["imageSize"][0]), int(p["imageSize"][1])) != (tex.width, tex.height):
+            raise ValueError("gParams.imageSize must equal the output texture size")
+        bufs = (vars["gBVHNodes"], vars["gTris"], vars["gVerts"])
+        if not all(isinstance(b, Buffer) and b.tensor is not None for b in bufs):
+            raise TypeError("gBVHNodes / gTris / gVerts must be Buffers filled with copy_from_numpy")
+        # validated once per contents (one device-to-host read of each buffer), then only launched
+        key = tuple((id(b), b._version) for b in bufs)
+        hit = self.device._mesh.get(key)
+        if hit is None:
+            nb, tb, vb = bufs
+            nodes = nb.to_numpy().view(np.float32).reshape(-1, 8)
+            tris = tb.to_numpy().view(np.uint32).reshape(-1, 4)
+            nverts = vb.tensor.numel() // 4
+            depth = _mesh.validate_bvh(nodes, tris, nverts)
+            m = _mesh.Mesh(nb.tensor, tb.tensor, vb.tensor, len(nodes), len(tris), nverts, depth)
+            self.device._mesh.clear()                       # one mesh at a time (the app has one); the entry keeps its buffers alive
+            hit = self.device._mesh[key] = (m, bufs)
+        _mesh.render_mesh(p, hit[0], out=tex.tensor, ext=e)
+
     def _sdf(self, tc, vars):
         tex = vars["render_texture"]
         if tc[0] != tex.width or tc[1] != tex.height:
@@ -259,6 +286,7 @@ class Device:
         self.skip_empty = bool(skip_empty)
         self._label_cells: Dict[tuple, tuple] = {}          # the cell-packed copy of the bound (gLabels, gPreds) pair
         self._mod4: Dict[tuple, tuple] = {}                 # the interleaved copy of the bound intensity buffers
+        self._mesh: Dict[tuple, tuple] = {}                 # the validated K4 mesh of the bound (gBVHNodes, gTris, gVerts)
 
     def load_program(self, path: Union[str, pathlib.Path], entry_points: Sequence[str]) -> Program:
         for ep in entry_points:
@@ -274,7 +302,7 @@ class Device:
                       usage=None) -> Buffer:
         return Buffer(self, element_count, element_size if element_size is not None else struct_size)
 
-    def create_texture(self, format: Format, width: int, height: int, usage=None) -> Texture:
+    def create_texture(self, format: Format, width: int, height: int, usage=None, label: Optional[str] = None) -> Texture:
         return Texture(self, format, width, height)
 
     def create_command_encoder(self) -> CommandEncoder:

@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .params import brats_params, render_ext, sdf_params, volume_params
+from .params import brats_params, mesh_params, render_ext, sdf_params, volume_params
 
 
 def load_native():
@@ -64,6 +64,11 @@ def pack_volume_params(p: Mapping[str, Any]) -> torch.Tensor:
 def pack_sdf_params(p: Mapping[str, Any], eye, U, V, W) -> torch.Tensor:
     """gParams + gEye/gU/gV/gW of scripts/raymarch/app.py:199-221 -> MrirtSdfParams bytes."""
     return _blob(sdf_params(p, eye, U, V, W))
+
+
+def pack_mesh_params(p: Mapping[str, Any]) -> torch.Tensor:
+    """gParams dict of scripts/mesh_rt/app.py:224-232 -> MrirtMeshParams bytes."""
+    return _blob(mesh_params(p))
 
 
 def _stream() -> C.c_void_p:
@@ -213,6 +218,35 @@ def render_sdf(params: torch.Tensor, width: int, height: int, like: torch.Tensor
 @render_sdf.register_fake
 def _(params, width, height, like):
     return torch.empty((height, width, 4), dtype=torch.float32, device=like.device)
+
+
+# --- K4 -----------------------------------------------------------------------------------------
+@torch.library.custom_op("mrirt::render_mesh", mutates_args=())
+def render_mesh(params: torch.Tensor, ext: torch.Tensor, nodes: torch.Tensor, tris: torch.Tensor, verts: torch.Tensor,
+                max_depth: int) -> torch.Tensor:
+    """compute_main (scripts/mesh_rt/mesh_rt.slang:138-164) through mrirt_render_mesh.  nodes: float32 [2N x 4], tris: int32
+    [M x 4], verts: float32 [V x 4] (mrirt.upload_mesh's buffers; the counts are taken from their sizes); max_depth: the
+    tree's depth (``Mesh.depth``).  The kernel stops, and paints, any ray that meets a malformed buffer; it never reads
+    outside these three tensors."""
+    P, E = _unblob(params, _lib.MeshParams), _unblob(ext, _lib.RenderExt)
+    n = _dev_flat(nodes, torch.float32, "gBVHNodes")
+    t = _dev_flat(tris, torch.int32, "gTris")
+    v = _dev_flat(verts, torch.float32, "gVerts")
+    dev = _one_device([("gBVHNodes", n), ("gTris", t), ("gVerts", v)])
+    dt = torch.float16 if E.outFormat == _lib.OUT_RGBA16F else torch.float32
+    with torch.cuda.device(dev):
+        out = torch.empty((int(P.imageSize[1]), int(P.imageSize[0]), 4), dtype=dt, device=dev)
+        rc = _lib.lib().mrirt_render_mesh(C.byref(P), C.byref(E), _ptr(n), n.numel() // 8, _ptr(t), t.numel() // 4, _ptr(v),
+                                          v.numel() // 4, int(max_depth), _ptr(out), int(P.imageSize[0]), None, None, _stream())
+    _lib.check(rc, "mrirt_render_mesh")
+    return out
+
+
+@render_mesh.register_fake
+def render_mesh_fake(params, ext, nodes, tris, verts, max_depth):
+    P, E = _unblob(params, _lib.MeshParams), _unblob(ext, _lib.RenderExt)
+    dt = torch.float16 if E.outFormat == _lib.OUT_RGBA16F else torch.float32
+    return torch.empty((int(P.imageSize[1]), int(P.imageSize[0]), 4), dtype=dt, device=nodes.device)
 
 
 # --- INR ----------------------------------------------------------------------------------------
