@@ -29,7 +29,7 @@ extern "C" {
 /* 4: MRIRT_LAYOUT_MOD4 + mrirt_build_mod4_grid (the four modalities of a BraTS case as ONE float4 grid: unshaded K1 and
  *    mrirt_render_brats_inr); the packed INR image ends in 32 KiB of slack more (mrirt_inr_pack_bytes says how much to allocate). */
 /*    Backward-compatible additions under the same version: MrirtMeshParams + mrirt_render_mesh (K4, the triangle-mesh BVH
- *    ray tracer), mrirt_sizeof(6). */
+ *    ray tracer), mrirt_sizeof(6); mrirt_edt_scratch_bytes, mrirt_edt_squared, mrirt_hausdorff (no new struct). */
 #define MRIRT_ABI_VERSION 4
 
 typedef enum MrirtStatus {
@@ -408,6 +408,29 @@ int mrirt_inr_forward_refined(const MrirtInrDesc* desc, const float* coords, con
 /* predict_volume (inr/inr/model.py:119-141): mods[M][H][W][D] fp32 -> pred[H][W][D] int16 */
 int mrirt_inr_predict_volume(const MrirtInrDesc* desc, const float* mods, const uint32_t hwd[3],
                              int16_t* pred, void* stream);
+
+/* ------------------------------------------------------------------------------------ */
+/* Exact distance transform and Hausdorff distance (inr/inr/model.py:164-195)            */
+/* ------------------------------------------------------------------------------------ */
+/* labels / pred / truth: the int16 [H][W][D] C-order volume mrirt_inr_predict_volume writes (device).  The coordinate of
+ * index i on axis k is c_k(i) = double(float(i) * spacing[k]); the squared distance field of a mask M is
+ *   F_M(x) = min over y in M of ((d0^2 + d1^2) + d2^2),  d_k = c_k(x_k) - c_k(y_k),
+ * every operation in unfused fp64 in that order, +inf everywhere when M is empty — bit for bit what a nearest-neighbour
+ * query over the reference's float32 coordinate grid returns, squared.
+ * Limits (checked before any HIP call): every axis in 1..4096 and H*W*D < 2^31 (MRIRT_ERR_DIMS); finite spacing whose
+ * product with the last index is finite too, num_classes in 1..32, scratch_bytes large enough (MRIRT_ERR_ARG).
+ * mrirt_edt_scratch_bytes: device bytes mrirt_hausdorff needs for num_classes in 1..32 (two fp64 fields + 32 B per class),
+ * what mrirt_edt_squared needs for num_classes == 0 (64: it runs in place in field_sq); 0 for a volume outside the limits. */
+int64_t mrirt_edt_scratch_bytes(const uint32_t hwd[3], uint32_t num_classes);
+/* field_sq[H][W][D] (device, fp64) = F_M for M = (labels == cls); any cls is valid (a class that does not occur: +inf) */
+int mrirt_edt_squared(const int16_t* labels, const uint32_t hwd[3], int32_t cls, const float spacing[3],
+                      double* field_sq, void* scratch, int64_t scratch_bytes, void* stream);
+/* For every class c < num_classes, P = (pred == c), T = (truth == c):
+ *   directed_sq[2c] = max over P of F_T, directed_sq[2c + 1] = max over T of F_P (device, fp64; both NaN when the class is
+ * absent from either volume); the reference's hausdorff[c] is sqrt(max of the two).  A label outside [0, num_classes)
+ * belongs to no class.  The result stays in device memory: nothing synchronises with the host. */
+int mrirt_hausdorff(const int16_t* pred, const int16_t* truth, const uint32_t hwd[3], const float spacing[3],
+                    uint32_t num_classes, double* directed_sq, void* scratch, int64_t scratch_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------ */
 /* Per-sample INR render, one call (BASELINE config 5)                                   */

@@ -17,7 +17,7 @@ CSRC = PKG_DIR / "csrc"
 INCLUDE = PKG_DIR.parent / "include"
 SO_PATH = pathlib.Path(os.environ.get("MRIRT_LIB", PKG_DIR / "libmrirt.so"))   # override: A/B builds in development
 HIP_SOURCES = ["brats_march.hip", "brats_slab.hip", "brats_ring.hip", "volume_march.hip", "grid_ops.hip", "inr_mlp.hip",
-               "mesh_rt.hip", "abort_trace.cpp"]
+               "mesh_rt.hip", "edt.hip", "abort_trace.cpp"]
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17", "-Wall"]
 
 # every extern "C" symbol include/mrirt.h declares
@@ -29,6 +29,7 @@ ABI_SYMBOLS = [
     "mrirt_detile", "mrirt_inr_pack_bytes", "mrirt_inr_pack_weights", "mrirt_inr_calibrate", "mrirt_inr_forward", "mrirt_inr_forward_refined",
     "mrirt_inr_predict_volume", "mrirt_abi_version", "mrirt_status_string", "mrirt_last_hip_error",
     "mrirt_sizeof", "mrirt_brats_skip_applicable", "mrirt_brats_kernel_family", "mrirt_install_abort_trace",
+    "mrirt_edt_scratch_bytes", "mrirt_edt_squared", "mrirt_hausdorff",
 ]
 
 ABI_VERSION = 4          # MRIRT_ABI_VERSION of include/mrirt.h this binding was written against
@@ -305,6 +306,12 @@ def lib() -> C.CDLL:
     l.mrirt_inr_forward_refined.argtypes = [C.POINTER(InrDesc), vp, vp, i64, vp, vp, vp]
     l.mrirt_inr_calibrate.argtypes = [C.POINTER(InrDesc), vp]
     l.mrirt_inr_predict_volume.argtypes = [C.POINTER(InrDesc), vp, C.POINTER(u32), vp, vp]
+    l.mrirt_edt_scratch_bytes.argtypes = [C.POINTER(u32), u32]
+    l.mrirt_edt_scratch_bytes.restype = i64
+    l.mrirt_edt_squared.argtypes = [vp, C.POINTER(u32), i32, C.POINTER(f32), vp, vp, i64, vp]
+    l.mrirt_edt_squared.restype = i32
+    l.mrirt_hausdorff.argtypes = [vp, vp, C.POINTER(u32), C.POINTER(f32), u32, vp, vp, i64, vp]
+    l.mrirt_hausdorff.restype = i32
     l.mrirt_status_string.argtypes = [i32]
     l.mrirt_status_string.restype = C.c_char_p
     l.mrirt_sizeof.argtypes = [u32]

@@ -194,6 +194,60 @@ Tensor inr_forward(const Tensor& weights, const Tensor& biases, int64_t kind, in
     return out;
 }
 
+// the volume's extent and spacing as the C ABI takes them; every label tensor is int16 (H, W, D) on one device
+void edt_args(const Tensor& first, const OptTensor& second, at::ArrayRef<double> spacing, uint32_t hwd[3], float sp[3],
+              std::optional<at::Device>& dev) {
+    dev_ptr(first, at::kShort, "labels");
+    dev_ptr(second, at::kShort, "labels");
+    same_device(dev, first, "labels");
+    same_device(dev, second, "labels");
+    TORCH_CHECK_VALUE(first.dim() == 3 && (!second.has_value() || second->sizes() == first.sizes()),
+                      "label volumes must be (H, W, D) int16 tensors of one shape");
+    TORCH_CHECK_VALUE(spacing.size() == 3, "spacing: expected three values");
+    for (int k = 0; k < 3; ++k) {
+        TORCH_CHECK_VALUE(first.size(k) <= 0xFFFFFFFFll, "axis too long");
+        hwd[k] = (uint32_t)first.size(k);
+        sp[k] = (float)spacing[k];
+    }
+}
+
+Tensor scratch_for(int64_t nbytes, at::Device dev) {
+    return at::empty({ std::max<int64_t>(nbytes, 8) / 8 }, at::TensorOptions().dtype(at::kLong).device(dev));
+}
+
+// exact squared Euclidean distance transform of (labels == cls) through mrirt_edt_squared
+Tensor edt_squared(const Tensor& labels, int64_t cls, at::ArrayRef<double> spacing) {
+    uint32_t hwd[3];
+    float sp[3];
+    std::optional<at::Device> dev;
+    edt_args(labels, std::nullopt, spacing, hwd, sp, dev);
+    TORCH_CHECK_VALUE(cls >= INT32_MIN && cls <= INT32_MAX, "cls out of range");
+    DeviceGuard guard(*dev);
+    const int64_t nbytes = mrirt_edt_scratch_bytes(hwd, 0);
+    Tensor out = at::empty(labels.sizes(), at::TensorOptions().dtype(at::kDouble).device(*dev));
+    Tensor scratch = scratch_for(nbytes, *dev);
+    check(mrirt_edt_squared(static_cast<const int16_t*>(labels.data_ptr()), hwd, (int32_t)cls, sp, out.data_ptr<double>(),
+                            scratch.data_ptr(), nbytes, current_stream()), "mrirt_edt_squared");
+    return out;
+}
+
+// squared directed Hausdorff distances [num_classes, 2] (inr/inr/model.py:164-195) through mrirt_hausdorff
+Tensor hausdorff(const Tensor& pred, const Tensor& truth, at::ArrayRef<double> spacing, int64_t num_classes) {
+    uint32_t hwd[3];
+    float sp[3];
+    std::optional<at::Device> dev;
+    edt_args(pred, truth, spacing, hwd, sp, dev);
+    TORCH_CHECK_VALUE(num_classes >= 1 && num_classes <= 32, "num_classes must be in [1, 32]");
+    DeviceGuard guard(*dev);
+    const int64_t nbytes = mrirt_edt_scratch_bytes(hwd, (uint32_t)num_classes);
+    Tensor out = at::empty({ num_classes, 2 }, at::TensorOptions().dtype(at::kDouble).device(*dev));
+    Tensor scratch = scratch_for(nbytes, *dev);
+    check(mrirt_hausdorff(static_cast<const int16_t*>(pred.data_ptr()), static_cast<const int16_t*>(truth.data_ptr()), hwd, sp,
+                          (uint32_t)num_classes, out.data_ptr<double>(), scratch.data_ptr(), nbytes, current_stream()),
+          "mrirt_hausdorff");
+    return out;
+}
+
 }  // namespace
 
 TORCH_LIBRARY(mrirt_native, m) {
@@ -203,6 +257,8 @@ TORCH_LIBRARY(mrirt_native, m) {
     m.def("render_mesh(Tensor params, Tensor ext, Tensor nodes, Tensor tris, Tensor verts, int max_depth) -> Tensor");
     m.def("inr_forward(Tensor weights, Tensor biases, int kind, int num_layers, int in_dim, int out_dim, int hidden, "
           "int fourier_freqs, int num_mods, float w0, Tensor? coords, Tensor? feats, int n) -> Tensor");
+    m.def("edt_squared(Tensor labels, int cls, float[] spacing) -> Tensor");
+    m.def("hausdorff(Tensor pred, Tensor truth, float[] spacing, int num_classes) -> Tensor");
 }
 
 // the parameter blocks are CPU tensors and the grids device tensors: no single dispatch key fits, so the
@@ -213,4 +269,6 @@ TORCH_LIBRARY_IMPL(mrirt_native, CompositeExplicitAutograd, m) {
     m.impl("render_sdf", &render_sdf);
     m.impl("render_mesh", &render_mesh);
     m.impl("inr_forward", &inr_forward);
+    m.impl("edt_squared", &edt_squared);
+    m.impl("hausdorff", &hausdorff);
 }

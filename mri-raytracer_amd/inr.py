@@ -266,6 +266,94 @@ def coverage_dice(pred, true) -> float:
     return (2 * int(h[1, 1]) + 1e-6) / (denom + 1e-6) if denom > 0 else 0.0
 
 
+def _label_volume(x, dev, what: str) -> torch.Tensor:
+    """A label volume (NumPy array or tensor, any integer dtype or bool) as the contiguous int16 (H, W, D) device tensor the
+    kernels read.  A value that int16 cannot hold is no class's label: it becomes -1 instead of wrapping into one."""
+    t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))
+    if t.dtype.is_floating_point or t.dtype.is_complex:
+        raise TypeError(f"{what}: expected integer labels, got {t.dtype}")
+    if t.dim() != 3:
+        raise ValueError(f"{what}: expected an (H, W, D) volume, got shape {tuple(t.shape)}")
+    t = t.to(dev)
+    if t.dtype not in (torch.int16, torch.int8, torch.uint8, torch.bool):
+        t = torch.where((t < -32768) | (t > 32767), torch.full_like(t, -1), t)
+    return t.to(torch.int16).contiguous()
+
+
+def _spacing3(spacing):
+    sp = [float(np.float32(s)) for s in spacing]
+    if len(sp) != 3:
+        raise ValueError("spacing: expected three values (one per axis)")
+    return (C.c_float * 3)(*sp)
+
+
+def hausdorff_directed_sq(pred, true, spacing=(1.0, 1.0, 1.0), num_classes: int = 4) -> torch.Tensor:
+    """(num_classes, 2) fp64 device tensor of ``mrirt_hausdorff``: [c, 0] = max over (pred == c) of the squared distance to
+    (true == c), [c, 1] the other direction; NaN where the class is absent from either volume.  No host synchronisation."""
+    dev = pred.device if isinstance(pred, torch.Tensor) and pred.is_cuda else (
+        true.device if isinstance(true, torch.Tensor) and true.is_cuda else _require_gpu())
+    p, t = _label_volume(pred, dev, "pred"), _label_volume(true, dev, "true")
+    if p.shape != t.shape:
+        raise ValueError(f"hausdorff: prediction {tuple(p.shape)} and ground truth {tuple(t.shape)} differ in shape")
+    hwd = (C.c_uint32 * 3)(*p.shape)
+    lib = _lib.lib()
+    with torch.cuda.device(dev):
+        nbytes = int(lib.mrirt_edt_scratch_bytes(hwd, int(num_classes)))
+        out = torch.empty((max(int(num_classes), 0), 2), dtype=torch.float64, device=dev)
+        scratch = torch.empty(max(nbytes, 8) // 8, dtype=torch.int64, device=dev)
+        rc = lib.mrirt_hausdorff(_ptr(p), _ptr(t), hwd, _spacing3(spacing), int(num_classes), _ptr(out), _ptr(scratch),
+                                 nbytes, _stream_ptr(None))
+    _lib.check(rc, "mrirt_hausdorff")
+    return out
+
+
+def hausdorff_distance(pred, true, spacing=(1.0, 1.0, 1.0), num_classes: int = 4) -> Dict[int, float]:
+    """Per-class symmetric Hausdorff distance of two label volumes (inr/inr/model.py:164-195) — bit for bit what the
+    reference's two cKDTrees per class return, from an exact fp64 distance transform on the GPU (csrc/edt.hip).  NumPy
+    arrays are uploaded, device tensors (what ``predict_volume`` returns) are used where they are; any integer dtype.
+    ``{c: float}``, NaN for a class that is absent from either volume."""
+    d = hausdorff_directed_sq(pred, true, spacing, num_classes).cpu().numpy()
+    out: Dict[int, float] = {}
+    for c in range(int(num_classes)):
+        a, b = float(d[c, 0]), float(d[c, 1])
+        out[c] = float(np.sqrt(np.float64(max(a, b)))) if a == a and b == b else float("nan")
+    return out
+
+
+def distance_transform(mask_or_labels, cls: Optional[int] = None, spacing=(1.0, 1.0, 1.0)) -> torch.Tensor:
+    """Exact squared Euclidean distance transform: fp64 (H, W, D) device tensor, at every voxel the squared distance to the
+    nearest voxel of the mask (itself included: 0 on the mask), +inf everywhere when the mask is empty.  ``cls=None``: the
+    mask is ``mask_or_labels != 0`` (a bool mask as is); otherwise ``mask_or_labels == cls``.  Coordinates are
+    ``float32(index) * float32(spacing)`` widened to fp64, as in ``hausdorff_distance``."""
+    dev = mask_or_labels.device if isinstance(mask_or_labels, torch.Tensor) and mask_or_labels.is_cuda else _require_gpu()
+    if cls is None:
+        m = mask_or_labels if isinstance(mask_or_labels, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(mask_or_labels))
+        lab, cls = _label_volume(m != 0, dev, "mask"), 1
+    else:
+        lab = _label_volume(mask_or_labels, dev, "labels")
+    hwd = (C.c_uint32 * 3)(*lab.shape)
+    lib = _lib.lib()
+    with torch.cuda.device(dev):
+        nbytes = int(lib.mrirt_edt_scratch_bytes(hwd, 0))
+        out = torch.empty(tuple(lab.shape), dtype=torch.float64, device=dev)
+        scratch = torch.empty(max(nbytes, 8) // 8, dtype=torch.int64, device=dev)
+        rc = lib.mrirt_edt_squared(_ptr(lab), hwd, int(cls), _spacing3(spacing), _ptr(out), _ptr(scratch), nbytes, _stream_ptr(None))
+    _lib.check(rc, "mrirt_edt_squared")
+    return out
+
+
+def evaluate_single_case(case_idx: int, case_data: Dict[str, Any], params, num_classes: int, fourier_freqs: int) -> Dict[str, Any]:
+    """model.py:198-214, the evaluation every notebook and train.py run after training: predict the case's volume, then
+    per-class Dice, Hausdorff (unit spacing, as the reference calls it), foreground Dice and the mean of the Dice scores
+    that are not NaN.  The prediction stays on the device between the steps; ``pred_vol`` is that device tensor."""
+    pred, seg = predict_volume(params, case_data, fourier_freqs)
+    dice = dice_score(pred, seg, num_classes)
+    finite = [v for v in dice.values() if v == v]
+    return dict(case_idx=case_idx, pred_vol=pred, true_vol=seg, case_data=case_data, class_scores=dice,
+                coverage_dice=coverage_dice(pred, seg), mean_dice=float(np.mean(finite)) if finite else 0.0,
+                hausdorff_scores=hausdorff_distance(pred, seg, num_classes=num_classes))
+
+
 _C5_SCRATCH: dict = {}
 
 

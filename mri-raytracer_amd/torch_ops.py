@@ -288,3 +288,55 @@ def inr_forward(weights: torch.Tensor, biases: torch.Tensor, kind: int, num_laye
 @inr_forward.register_fake
 def _(weights, biases, kind, num_layers, in_dim, out_dim, hidden, fourier_freqs, num_mods, w0, coords, feats, n):
     return torch.empty((n, out_dim), dtype=torch.float32, device=weights.device)
+
+
+# --- exact distance transform / Hausdorff -------------------------------------------------------
+def _edt_args(labels: Sequence, spacing: Sequence[float]):
+    vols = [_dev_flat(v, torch.int16, what) for what, v in labels]
+    if any(v.dim() != 3 or v.shape != vols[0].shape for v in vols):
+        raise ValueError("label volumes must be (H, W, D) int16 tensors of one shape")
+    if len(spacing) != 3:
+        raise ValueError("spacing: expected three values")
+    return vols, (C.c_uint32 * 3)(*vols[0].shape), (C.c_float * 3)(*[float(np.float32(s)) for s in spacing])
+
+
+@torch.library.custom_op("mrirt::edt_squared", mutates_args=())
+def edt_squared(labels: torch.Tensor, cls: int, spacing: Sequence[float]) -> torch.Tensor:
+    """fp64 (H, W, D): squared distance of every voxel to the nearest voxel with ``labels == cls`` (+inf when there is
+    none), coordinates ``float32(index) * float32(spacing)`` — mrirt_edt_squared, exact."""
+    (lab,), hwd, sp = _edt_args([("labels", labels)], spacing)
+    lib = _lib.lib()
+    with torch.cuda.device(lab.device):
+        nbytes = int(lib.mrirt_edt_scratch_bytes(hwd, 0))
+        out = torch.empty(tuple(lab.shape), dtype=torch.float64, device=lab.device)
+        scratch = torch.empty(max(nbytes, 8) // 8, dtype=torch.int64, device=lab.device)
+        rc = lib.mrirt_edt_squared(_ptr(lab), hwd, int(cls), sp, _ptr(out), _ptr(scratch), nbytes, _stream())
+    _lib.check(rc, "mrirt_edt_squared")
+    return out
+
+
+@edt_squared.register_fake
+def _(labels, cls, spacing):
+    return torch.empty(tuple(labels.shape), dtype=torch.float64, device=labels.device)
+
+
+@torch.library.custom_op("mrirt::hausdorff", mutates_args=())
+def hausdorff(pred: torch.Tensor, truth: torch.Tensor, spacing: Sequence[float], num_classes: int) -> torch.Tensor:
+    """fp64 (num_classes, 2) squared directed Hausdorff distances of two int16 (H, W, D) label volumes (mrirt_hausdorff):
+    [c, 0] = max over (pred == c) of the squared distance to (truth == c), [c, 1] the other direction, NaN where the class
+    is absent from either; inr/inr/model.py:164-195's value for class c is ``sqrt(max of the row)``."""
+    (p, t), hwd, sp = _edt_args([("pred", pred), ("truth", truth)], spacing)
+    dev = _one_device([("pred", p), ("truth", t)])
+    lib = _lib.lib()
+    with torch.cuda.device(dev):
+        nbytes = int(lib.mrirt_edt_scratch_bytes(hwd, int(num_classes)))
+        out = torch.empty((max(int(num_classes), 0), 2), dtype=torch.float64, device=dev)
+        scratch = torch.empty(max(nbytes, 8) // 8, dtype=torch.int64, device=dev)
+        rc = lib.mrirt_hausdorff(_ptr(p), _ptr(t), hwd, sp, int(num_classes), _ptr(out), _ptr(scratch), nbytes, _stream())
+    _lib.check(rc, "mrirt_hausdorff")
+    return out
+
+
+@hausdorff.register_fake
+def _(pred, truth, spacing, num_classes):
+    return torch.empty((num_classes, 2), dtype=torch.float64, device=pred.device)
