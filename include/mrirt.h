@@ -29,7 +29,8 @@ extern "C" {
 /* 4: MRIRT_LAYOUT_MOD4 + mrirt_build_mod4_grid (the four modalities of a BraTS case as ONE float4 grid: unshaded K1 and
  *    mrirt_render_brats_inr); the packed INR image ends in 32 KiB of slack more (mrirt_inr_pack_bytes says how much to allocate). */
 /*    Backward-compatible additions under the same version: MrirtMeshParams + mrirt_render_mesh (K4, the triangle-mesh BVH
- *    ray tracer), mrirt_sizeof(6); mrirt_edt_scratch_bytes, mrirt_edt_squared, mrirt_hausdorff (no new struct). */
+ *    ray tracer), mrirt_sizeof(6); mrirt_edt_scratch_bytes, mrirt_edt_squared, mrirt_hausdorff (no new struct);
+ *    mrirt_surface_scratch_bytes, mrirt_surface_count, mrirt_surface_extract (no new struct). */
 #define MRIRT_ABI_VERSION 4
 
 typedef enum MrirtStatus {
@@ -431,6 +432,39 @@ int mrirt_edt_squared(const int16_t* labels, const uint32_t hwd[3], int32_t cls,
  * belongs to no class.  The result stays in device memory: nothing synchronises with the host. */
 int mrirt_hausdorff(const int16_t* pred, const int16_t* truth, const uint32_t hwd[3], const float spacing[3],
                     uint32_t num_classes, double* directed_sq, void* scratch, int64_t scratch_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------ */
+/* Class surfaces from label volumes (naive surface nets), the input of K4                */
+/* ------------------------------------------------------------------------------------ */
+/* labels: the int16 [n0][n1][n2] C-order volume of mrirt_inr_predict_volume / mrirt_hausdorff (device); axis k is world axis
+ * k.  Voxel v is inside iff 0 <= labels[v] < 32 and bit labels[v] of class_mask is set; every voxel outside the volume is
+ * outside, so surfaces close at the volume's faces.  Cell c (0 <= c_k <= n_k, linear index (c0 (n1+1) + c1)(n2+1) + c2) has
+ * the voxels c - 1 + b, b in {0,1}^3, as corners and is active when they are neither all inside nor all outside.
+ *   vertex of an active cell: over its edges whose two corners differ (from corner b along axis a, b_a = 0) S_k = sum of
+ *     2 b_k + (k == a) and m their number; q_k = float(S_k) / float(2 m), x_k = (float(c_k - 1) + q_k) * spacing[k] + origin[k],
+ *     every operation a separate float32 one.  Vertices are numbered in increasing linear cell index.
+ *   quads: cell c owns the lattice edge from voxel c - 1 to c - 1 + e_a when c_b >= 1 and c_c >= 1, (a, b, c) one of (0,1,2),
+ *     (1,2,0), (2,0,1).  An owned edge whose voxels differ emits the quad Q(ib, ic) = vertex of cell c - (1-ib) e_b - (1-ic) e_c
+ *     as the triangles (Q00, Q10, Q11), (Q00, Q11, Q01) when voxel c - 1 is inside (normal along +a), else (Q00, Q11, Q10),
+ *     (Q00, Q01, Q11); quads are ordered by owning cell, then by a.
+ * The mesh is closed and oriented outwards.  With origin = volMin and spacing = voxelSize of MrirtBratsParams it lies on
+ * the K1 volume (K1 samples lattice points, no half-voxel offset).
+ * Limits (checked before any HIP call): every extent >= 1 (MRIRT_ERR_DIMS); (n0+1)(n1+1)(n2+1) <= 2^31 - 1, finite
+ * spacing > 0, finite origin, vert_cap / tri_cap >= 0, scratch 16-byte aligned and scratch_bytes large enough (MRIRT_ERR_ARG).
+ * mrirt_surface_scratch_bytes: device bytes both calls need (5 B per cell + 16 B per 1024 cells, rounded up); 0 for a
+ * volume outside the limits. */
+int64_t mrirt_surface_scratch_bytes(const uint32_t hwd[3]);
+/* counts_dev (device, int64[2]) = { vertices V, triangles T } of the class set's surface; an empty set gives { 0, 0 }.
+ * Nothing synchronises with the host. */
+int mrirt_surface_count(const int16_t* labels, const uint32_t hwd[3], uint32_t class_mask, void* scratch, int64_t scratch_bytes,
+                        int64_t* counts_dev, void* stream);
+/* verts (device, float32 [vert_cap][3]) and tris (device, int32 [tri_cap][3]) receive the mesh.  Complete on its own (no
+ * earlier mrirt_surface_count needed): counts_dev is always written; geometry is written only when V <= vert_cap AND
+ * T <= tri_cap, and then exactly V vertices and T triangles — nothing past them.  verts / tris may be NULL when their
+ * capacity is 0. */
+int mrirt_surface_extract(const int16_t* labels, const uint32_t hwd[3], uint32_t class_mask, const float spacing[3],
+                          const float origin[3], float* verts, int64_t vert_cap, int32_t* tris, int64_t tri_cap,
+                          void* scratch, int64_t scratch_bytes, int64_t* counts_dev, void* stream);
 
 /* ------------------------------------------------------------------------------------ */
 /* Per-sample INR render, one call (BASELINE config 5)                                   */

@@ -5,7 +5,7 @@ the task-mandated name ``mri-raytracer_amd``.  Layout:
   csrc/       hand-written gfx950 HIP kernels + the C ABI (include/mrirt.h) -> libmrirt.so
   _lib.py     ctypes binding (fails loudly when the library is missing — no CPU fallback)
   render.py   render_brats / render_volume_u8 / render_sdf over device tensors
-  mesh.py     K4: PLY loading, the reference's BVH, upload + validation, render_mesh
+  mesh.py     K4: PLY loading, the reference's BVH, upload + validation, render_mesh; class surfaces of label volumes
   shim.py     slangpy-shaped ``Device`` / ``ComputeKernel.dispatch(thread_count, vars, ...)``
   camera.py   OrbitalCamera (both reference variants)
   volume.py   load-time volume preparation (normalise, flatten, world frame, u8 pack, BC4)
@@ -16,7 +16,8 @@ the task-mandated name ``mri-raytracer_amd``.  Layout:
 from . import _lib, camera, inr, mesh, nifti, params, render, shim, synth, tiles, torch_ops, viewer, volume  # noqa: F401
 from .camera import OrbitalCamera  # noqa: F401
 from .inr import apply_mlp, build_input, inr_forward, model_load, predict_volume, render_brats_inr  # noqa: F401
-from .mesh import build_bvh, load_ply, normalize_mesh, render_mesh, upload_mesh  # noqa: F401
+from .mesh import (build_bvh, extract_surface, load_ply, normalize_mesh, render_mesh, surface_mesh,  # noqa: F401
+                   upload_mesh)
 from .shim import Device, KernelShim  # noqa: F401
 from .render import (Grid, detile, render_brats, render_sdf, render_volume_u8, tiles_for_rank,  # noqa: F401
                      unbrick_grid, upload_grid, upload_label_cells, upload_mod4)

@@ -17,7 +17,7 @@ CSRC = PKG_DIR / "csrc"
 INCLUDE = PKG_DIR.parent / "include"
 SO_PATH = pathlib.Path(os.environ.get("MRIRT_LIB", PKG_DIR / "libmrirt.so"))   # override: A/B builds in development
 HIP_SOURCES = ["brats_march.hip", "brats_slab.hip", "brats_ring.hip", "volume_march.hip", "grid_ops.hip", "inr_mlp.hip",
-               "mesh_rt.hip", "edt.hip", "abort_trace.cpp"]
+               "mesh_rt.hip", "edt.hip", "surface.hip", "abort_trace.cpp"]
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17", "-Wall"]
 
 # every extern "C" symbol include/mrirt.h declares
@@ -30,6 +30,7 @@ ABI_SYMBOLS = [
     "mrirt_inr_predict_volume", "mrirt_abi_version", "mrirt_status_string", "mrirt_last_hip_error",
     "mrirt_sizeof", "mrirt_brats_skip_applicable", "mrirt_brats_kernel_family", "mrirt_install_abort_trace",
     "mrirt_edt_scratch_bytes", "mrirt_edt_squared", "mrirt_hausdorff",
+    "mrirt_surface_scratch_bytes", "mrirt_surface_count", "mrirt_surface_extract",
 ]
 
 ABI_VERSION = 4          # MRIRT_ABI_VERSION of include/mrirt.h this binding was written against
@@ -312,6 +313,12 @@ def lib() -> C.CDLL:
     l.mrirt_edt_squared.restype = i32
     l.mrirt_hausdorff.argtypes = [vp, vp, C.POINTER(u32), C.POINTER(f32), u32, vp, vp, i64, vp]
     l.mrirt_hausdorff.restype = i32
+    l.mrirt_surface_scratch_bytes.argtypes = [C.POINTER(u32)]
+    l.mrirt_surface_scratch_bytes.restype = i64
+    l.mrirt_surface_count.argtypes = [vp, C.POINTER(u32), u32, vp, i64, vp, vp]
+    l.mrirt_surface_count.restype = i32
+    l.mrirt_surface_extract.argtypes = [vp, C.POINTER(u32), u32, C.POINTER(f32), C.POINTER(f32), vp, i64, vp, i64, vp, i64, vp, vp]
+    l.mrirt_surface_extract.restype = i32
     l.mrirt_status_string.argtypes = [i32]
     l.mrirt_status_string.restype = C.c_char_p
     l.mrirt_sizeof.argtypes = [u32]

@@ -13,6 +13,7 @@
 
 #include <cstring>
 #include <optional>
+#include <tuple>
 
 #include "mrirt.h"
 
@@ -248,6 +249,53 @@ Tensor hausdorff(const Tensor& pred, const Tensor& truth, at::ArrayRef<double> s
     return out;
 }
 
+// the surface of the voxels whose label's bit is set in class_mask (naive surface nets): a (H, W, D) int16 device volume
+int64_t surface_args(const Tensor& labels, int64_t class_mask, uint32_t hwd[3]) {
+    dev_ptr(labels, at::kShort, "labels");
+    TORCH_CHECK_VALUE(labels.dim() == 3, "labels must be an (H, W, D) int16 tensor");
+    TORCH_CHECK_VALUE(class_mask >= 0 && class_mask <= 0xFFFFFFFFll, "class_mask: expected a uint32 bit set (bit l = label l is inside)");
+    for (int k = 0; k < 3; ++k) {
+        TORCH_CHECK_VALUE(labels.size(k) <= 0xFFFFFFFFll, "axis too long");
+        hwd[k] = (uint32_t)labels.size(k);
+    }
+    const int64_t nbytes = mrirt_surface_scratch_bytes(hwd);
+    TORCH_CHECK_VALUE(nbytes > 0, "the volume is outside the supported sizes");
+    return nbytes;
+}
+
+// int64 [2]: vertices and triangles, through mrirt_surface_count
+Tensor surface_count(const Tensor& labels, int64_t class_mask) {
+    uint32_t hwd[3];
+    const int64_t nbytes = surface_args(labels, class_mask, hwd);
+    DeviceGuard guard(labels.device());
+    Tensor counts = at::empty({ 2 }, at::TensorOptions().dtype(at::kLong).device(labels.device()));
+    Tensor scratch = scratch_for(nbytes + 8, labels.device());
+    check(mrirt_surface_count(static_cast<const int16_t*>(labels.data_ptr()), hwd, (uint32_t)class_mask, scratch.data_ptr(), nbytes,
+                              counts.data_ptr<int64_t>(), current_stream()), "mrirt_surface_count");
+    return counts;
+}
+
+// (verts float32 [num_verts, 3], tris int32 [num_tris, 3]) through mrirt_surface_extract; zeroed where nothing is written
+std::tuple<Tensor, Tensor> surface_extract(const Tensor& labels, int64_t class_mask, at::ArrayRef<double> spacing,
+                                           at::ArrayRef<double> origin, int64_t num_verts, int64_t num_tris) {
+    uint32_t hwd[3];
+    const int64_t nbytes = surface_args(labels, class_mask, hwd);
+    TORCH_CHECK_VALUE(spacing.size() == 3 && origin.size() == 3, "spacing / origin: expected three values each");
+    TORCH_CHECK_VALUE(num_verts >= 0 && num_tris >= 0, "num_verts / num_tris must not be negative");
+    float sp[3], org[3];
+    for (int k = 0; k < 3; ++k) { sp[k] = (float)spacing[k]; org[k] = (float)origin[k]; }
+    DeviceGuard guard(labels.device());
+    Tensor verts = at::zeros({ num_verts, 3 }, at::TensorOptions().dtype(at::kFloat).device(labels.device()));
+    Tensor tris = at::zeros({ num_tris, 3 }, at::TensorOptions().dtype(at::kInt).device(labels.device()));
+    Tensor counts = at::empty({ 2 }, at::TensorOptions().dtype(at::kLong).device(labels.device()));
+    Tensor scratch = scratch_for(nbytes + 8, labels.device());
+    check(mrirt_surface_extract(static_cast<const int16_t*>(labels.data_ptr()), hwd, (uint32_t)class_mask, sp, org,
+                                num_verts ? verts.data_ptr<float>() : nullptr, num_verts, num_tris ? tris.data_ptr<int32_t>() : nullptr,
+                                num_tris, scratch.data_ptr(), nbytes, counts.data_ptr<int64_t>(), current_stream()),
+          "mrirt_surface_extract");
+    return { verts, tris };
+}
+
 }  // namespace
 
 TORCH_LIBRARY(mrirt_native, m) {
@@ -259,6 +307,8 @@ TORCH_LIBRARY(mrirt_native, m) {
           "int fourier_freqs, int num_mods, float w0, Tensor? coords, Tensor? feats, int n) -> Tensor");
     m.def("edt_squared(Tensor labels, int cls, float[] spacing) -> Tensor");
     m.def("hausdorff(Tensor pred, Tensor truth, float[] spacing, int num_classes) -> Tensor");
+    m.def("surface_count(Tensor labels, int class_mask) -> Tensor");
+    m.def("surface_extract(Tensor labels, int class_mask, float[] spacing, float[] origin, int num_verts, int num_tris) -> (Tensor, Tensor)");
 }
 
 // the parameter blocks are CPU tensors and the grids device tensors: no single dispatch key fits, so the
@@ -271,4 +321,6 @@ TORCH_LIBRARY_IMPL(mrirt_native, CompositeExplicitAutograd, m) {
     m.impl("inr_forward", &inr_forward);
     m.impl("edt_squared", &edt_squared);
     m.impl("hausdorff", &hausdorff);
+    m.impl("surface_count", &surface_count);
+    m.impl("surface_extract", &surface_extract);
 }

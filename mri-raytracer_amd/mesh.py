@@ -5,13 +5,15 @@
   build_bvh       the reference's median-split BVH, element for element, built level by level
   upload_mesh     host-side validation (once) + the device buffers app.py uploads (float4 nodes, uint4 tris, float4 verts)
   render_mesh     compute_main on the current stream (mrirt_render_mesh), no synchronisation
+  extract_surface the surface of a set of classes of a label volume as a triangle mesh (naive surface nets, csrc/surface.hip)
+  surface_mesh    extract_surface + build_bvh + upload_mesh: a label volume to a mesh render_mesh draws
 """
 from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass
 from pathlib import Path
-from typing import Any, Dict, Mapping, Optional, Tuple, Union
+from typing import Any, Dict, Iterable, Mapping, Optional, Tuple, Union
 
 import numpy as np
 
@@ -420,6 +422,77 @@ def render_mesh(params: Mapping[str, Any], mesh: Mesh, out=None, ext: Optional[M
             s = st.cpu()
             return o, {"pops": int(s[0]), "tests": int(s[1])}
     return o
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# class surfaces of label volumes
+# ------------------------------------------------------------------------------------------------------------------
+def class_mask(classes: Union[int, Iterable[int]]) -> int:
+    """The uint32 class set of mrirt_surface_*: bit l is set when label l is inside.  ``classes``: a label or an iterable
+    of labels, each in 0..31."""
+    try:
+        labels = [int(c) for c in classes]              # type: ignore[union-attr]
+    except TypeError:
+        labels = [int(classes)]                         # type: ignore[arg-type]
+    mask = 0
+    for c in labels:
+        if not 0 <= c < 32:
+            raise ValueError(f"classes: label {c} outside 0..31")
+        mask |= 1 << c
+    return mask
+
+
+def _frame3(values, what: str):
+    v = [float(np.float32(x)) for x in values]
+    if len(v) != 3:
+        raise ValueError(f"{what}: expected three values (one per axis)")
+    return (C.c_float * 3)(*v)
+
+
+def extract_surface(labels, classes, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0), stream=None):
+    """The surface of the voxels whose label is in ``classes`` (an int or an iterable of labels in 0..31; ``(1, 2, 3)`` is the
+    whole tumour) as a closed, outward-oriented triangle mesh — naive surface nets on the GPU (csrc/surface.hip), element
+    for element the definition of DESIGN.md section 12.  ``labels``: an (H, W, D) integer volume, a NumPy array or a device
+    tensor (what ``predict_volume`` returns); axis k is world axis k, voxel i at ``origin + i * spacing``.
+    Returns device tensors ``(verts float32 [V, 3], tris int32 [T, 3])``; an empty class gives two empty tensors.
+    One host read (the two counts) between ``mrirt_surface_count`` and ``mrirt_surface_extract``."""
+    import torch
+    from .inr import _label_volume
+    from .render import _on_stream, _ptr, _require_gpu, _stream_ptr
+    mask = class_mask(classes)
+    sp, org = _frame3(spacing, "spacing"), _frame3(origin, "origin")
+    dev = labels.device if isinstance(labels, torch.Tensor) and labels.is_cuda else _require_gpu()
+    lib = _lib.lib()
+    with torch.cuda.device(dev), _on_stream(stream):
+        lab = _label_volume(labels, dev, "labels")
+        hwd = (C.c_uint32 * 3)(*lab.shape)
+        nbytes = int(lib.mrirt_surface_scratch_bytes(hwd))
+        if nbytes <= 0:
+            raise ValueError(f"extract_surface: a volume of shape {tuple(lab.shape)} is outside the supported sizes")
+        scratch = torch.empty(nbytes // 8 + 1, dtype=torch.int64, device=dev)
+        counts = torch.empty(2, dtype=torch.int64, device=dev)
+        _lib.check(lib.mrirt_surface_count(_ptr(lab), hwd, mask, _ptr(scratch), nbytes, _ptr(counts), _stream_ptr(stream)),
+                   "mrirt_surface_count")
+        nv, nt = (int(x) for x in counts.cpu())
+        verts = torch.empty((nv, 3), dtype=torch.float32, device=dev)
+        tris = torch.empty((nt, 3), dtype=torch.int32, device=dev)
+        _lib.check(lib.mrirt_surface_extract(_ptr(lab), hwd, mask, sp, org, _ptr(verts) if nv else None, nv,
+                                             _ptr(tris) if nt else None, nt, _ptr(scratch), nbytes, _ptr(counts),
+                                             _stream_ptr(stream)), "mrirt_surface_extract")
+    return verts, tris
+
+
+def surface_mesh(labels, classes, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0), max_leaf_tris: int = 4) -> Mesh:
+    """A label volume to a mesh :func:`render_mesh` draws: :func:`extract_surface`, the reference's BVH on the host
+    (:func:`build_bvh`), :func:`upload_mesh`.  With ``origin = volMin`` and ``spacing = voxelSize`` of
+    ``volume.world_frame`` the surface lies on the K1 volume.  ValueError for an empty surface and for one beyond K4's
+    2^23 triangle limit."""
+    verts, tris = extract_surface(labels, classes, spacing, origin)
+    if tris.shape[0] == 0:
+        raise ValueError("surface_mesh: the surface is empty (no voxel of the volume has a label in `classes`)")
+    if tris.shape[0] >= MAX_INDEX or verts.shape[0] >= MAX_INDEX:
+        raise ValueError(f"surface_mesh: {tris.shape[0]} triangles / {verts.shape[0]} vertices are beyond K4's limit of 2^23")
+    return upload_mesh(build_bvh(verts.cpu().numpy(), tris.cpu().numpy(), max_leaf_tris))
 
 
 # ------------------------------------------------------------------------------------------------------------------

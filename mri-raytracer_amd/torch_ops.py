@@ -16,7 +16,7 @@ C++ extension (``load_native()`` -> ``torch.ops.mrirt_native.*``, csrc/torch_bin
 from __future__ import annotations
 
 import ctypes as C
-from typing import Any, Mapping, Optional, Sequence
+from typing import Any, Mapping, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -340,3 +340,66 @@ def hausdorff(pred: torch.Tensor, truth: torch.Tensor, spacing: Sequence[float],
 @hausdorff.register_fake
 def _(pred, truth, spacing, num_classes):
     return torch.empty((num_classes, 2), dtype=torch.float64, device=pred.device)
+
+
+# --- class surfaces of label volumes (naive surface nets) ---------------------------------------
+def _surface_args(labels: torch.Tensor, class_mask: int):
+    lab = _dev_flat(labels, torch.int16, "labels")
+    if lab.dim() != 3:
+        raise ValueError("labels must be an (H, W, D) int16 tensor")
+    if not 0 <= int(class_mask) <= 0xFFFFFFFF:
+        raise ValueError("class_mask: expected a uint32 bit set (bit l = label l is inside)")
+    hwd = (C.c_uint32 * 3)(*lab.shape)
+    nbytes = int(_lib.lib().mrirt_surface_scratch_bytes(hwd))
+    if nbytes <= 0:
+        raise ValueError(f"a volume of shape {tuple(lab.shape)} is outside the supported sizes")
+    return lab, hwd, nbytes
+
+
+@torch.library.custom_op("mrirt::surface_count", mutates_args=())
+def surface_count(labels: torch.Tensor, class_mask: int) -> torch.Tensor:
+    """int64 [2] on the device: vertices and triangles of the surface of the voxels whose label's bit is set in
+    ``class_mask`` (mrirt_surface_count).  No host synchronisation."""
+    lab, hwd, nbytes = _surface_args(labels, class_mask)
+    with torch.cuda.device(lab.device):
+        counts = torch.empty(2, dtype=torch.int64, device=lab.device)
+        scratch = torch.empty(nbytes // 8 + 1, dtype=torch.int64, device=lab.device)
+        rc = _lib.lib().mrirt_surface_count(_ptr(lab), hwd, int(class_mask), _ptr(scratch), nbytes, _ptr(counts), _stream())
+    _lib.check(rc, "mrirt_surface_count")
+    return counts
+
+
+@surface_count.register_fake
+def _(labels, class_mask):
+    return torch.empty(2, dtype=torch.int64, device=labels.device)
+
+
+@torch.library.custom_op("mrirt::surface_extract", mutates_args=())
+def surface_extract(labels: torch.Tensor, class_mask: int, spacing: Sequence[float], origin: Sequence[float], num_verts: int,
+                    num_tris: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(verts float32 [num_verts, 3], tris int32 [num_tris, 3]) of mrirt_surface_extract; the two sizes are the static
+    shapes of the outputs — the values of ``surface_count``.  With sizes smaller than the surface nothing is written (the
+    tensors come back zeroed); larger ones leave the rows past the surface zero.  No host synchronisation."""
+    lab, hwd, nbytes = _surface_args(labels, class_mask)
+    if len(spacing) != 3 or len(origin) != 3:
+        raise ValueError("spacing / origin: expected three values each")
+    if num_verts < 0 or num_tris < 0:
+        raise ValueError("num_verts / num_tris must not be negative")
+    sp = (C.c_float * 3)(*[float(np.float32(v)) for v in spacing])
+    org = (C.c_float * 3)(*[float(np.float32(v)) for v in origin])
+    with torch.cuda.device(lab.device):
+        verts = torch.zeros((int(num_verts), 3), dtype=torch.float32, device=lab.device)
+        tris = torch.zeros((int(num_tris), 3), dtype=torch.int32, device=lab.device)
+        counts = torch.empty(2, dtype=torch.int64, device=lab.device)
+        scratch = torch.empty(nbytes // 8 + 1, dtype=torch.int64, device=lab.device)
+        rc = _lib.lib().mrirt_surface_extract(_ptr(lab), hwd, int(class_mask), sp, org, _ptr(verts) if num_verts else None,
+                                              int(num_verts), _ptr(tris) if num_tris else None, int(num_tris), _ptr(scratch),
+                                              nbytes, _ptr(counts), _stream())
+    _lib.check(rc, "mrirt_surface_extract")
+    return verts, tris
+
+
+@surface_extract.register_fake
+def _(labels, class_mask, spacing, origin, num_verts, num_tris):
+    return (torch.empty((num_verts, 3), dtype=torch.float32, device=labels.device),
+            torch.empty((num_tris, 3), dtype=torch.int32, device=labels.device))
