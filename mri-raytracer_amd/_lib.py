@@ -16,7 +16,7 @@ PKG_DIR = pathlib.Path(__file__).resolve().parent
 CSRC = PKG_DIR / "csrc"
 INCLUDE = PKG_DIR.parent / "include"
 SO_PATH = pathlib.Path(os.environ.get("MRIRT_LIB", PKG_DIR / "libmrirt.so"))   # override: A/B builds in development
-HIP_SOURCES = ["brats_march.hip", "brats_slab.hip", "brats_ring.hip", "volume_march.hip", "grid_ops.hip", "inr_mlp.hip",
+HIP_SOURCES = ["brats_march.hip", "brats_skip.hip", "brats_c5.hip", "brats_slab.hip", "brats_ring.hip", "volume_march.hip", "grid_ops.hip", "inr_mlp.hip",
                "mesh_rt.hip", "edt.hip", "surface.hip", "abort_trace.cpp"]
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17", "-Wall"]
 
@@ -128,6 +128,7 @@ class MrirtError(RuntimeError):
 
 
 OBJ_DIR = PKG_DIR / "build"          # per-source objects (git-ignored; they do not travel to history)
+MAX_BUILD_JOBS = 16                  # compilers at once: os.cpu_count() is the whole machine's, a job may own far fewer
 
 
 def _hipcc() -> str:
@@ -173,7 +174,7 @@ def build(force: bool = False, verbose: bool = False, check: bool = True) -> pat
 
     def run(cmd):
         return cmd, subprocess.run(cmd, capture_output=True, text=True)
-    with ThreadPoolExecutor(max_workers=min(len(jobs), os.cpu_count() or 1) or 1) as pool:
+    with ThreadPoolExecutor(max_workers=min(len(jobs), os.cpu_count() or 1, MAX_BUILD_JOBS) or 1) as pool:
         for cmd, r in pool.map(run, jobs):
             if verbose or r.returncode != 0:
                 print(" ".join(cmd))

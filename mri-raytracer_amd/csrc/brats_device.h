@@ -1,5 +1,5 @@
-// Device code shared by the K1 march kernels (brats_march.hip: the register-gather kernels; brats_slab.hip: the
-// LDS-staged kernel): the kernel argument block, sampleLinear's cell arithmetic, the gathers of one cell per layout
+// Device code shared by the K1 march kernels (brats_march.hip: the register-gather kernels; brats_slab.hip, brats_ring.hip:
+// the LDS-staged kernels) and the C5 passes (brats_c5.hip): the kernel argument block, sampleLinear's cell arithmetic, the gathers of one cell per layout
 // (Taps), the transfer function + compositing step, ray set-up.  Reference: inr/viewer/brats_rt.slang:36-168.
 #pragma once
 #include "mrirt_host.h"
@@ -514,10 +514,5 @@ __device__ __forceinline__ void finish(const K1Args& a, int kind, int64_t oidx, 
         wave_count_add(a.stats + 1, r.nShaded);
     }
 }
-
-// brats_slab.hip: the LDS-staged march (VGA layout, one modality, no overlays), selected by brats_march.hip
-int launch_slab_march(const K1Args& a, bool strict, bool shade, hipStream_t s);
-// brats_ring.hip: the plane-synchronous LDS ring march (same launches)
-int launch_ring_march(const K1Args& a, bool strict, bool shade, hipStream_t s);
 
 }  // namespace mrirt

@@ -1,0 +1,32 @@
+// The host-side seam between the K1 units: what brats_march.hip (the march, its plan and prepare()), brats_skip.hip (the
+// skipping pre-pass), brats_c5.hip (the per-sample INR render), brats_slab.hip / brats_ring.hip (the LDS marches) and
+// inr_mlp.hip call across translation units.  tests/native/index_harness.hip reaches prepare() through this header.
+#pragma once
+#include "brats_device.h"
+
+namespace mrirt {
+
+// what prepare() decodes of MrirtRenderExt besides the kernel arguments (kernelVariant: see prepare(), brats_march.hip)
+struct Prepared { uint32_t layout, math; bool shade, pipe, slab, ring, leap, tag; };
+
+// brats_march.hip: validate + fill the kernel arguments shared by every K1 and C5 entry point
+int prepare(const MrirtBratsParams* p, const MrirtRenderExt* ext, const void* const vol[4],
+            const void* labels, const void* preds, bool needVolumes, int64_t pitch_px,
+            K1Args& a, Prepared& cfg);
+
+// brats_skip.hip: the pre-pass of a skipping launch.  Builds the empty-radius map of `a`'s configuration in skip->mask
+// on `s` (unless skip->mapReady: the caller vouches that the scratch already holds it) and points a.skipDist / a.mX,
+// mXY, mY, mZ at it.
+int launch_skip_prepass(const MrirtBratsParams* p, const MrirtSkip* skip, bool strict, hipStream_t s, K1Args& a);
+
+// brats_slab.hip: the LDS-staged march (VGA layout, one modality, no overlays), selected by brats_march.hip
+int launch_slab_march(const K1Args& a, bool strict, bool shade, hipStream_t s);
+// brats_ring.hip: the plane-synchronous LDS ring march (same launches)
+int launch_ring_march(const K1Args& a, bool strict, bool shade, hipStream_t s);
+
+// inr_mlp.hip: the MLP forward with the point count in device memory (argmax only); segTicket: nullptr, or a zeroed device
+// word the near-tie refinement deals its segments with
+int inr_forward_dev_n(const MrirtInrDesc* desc, const float* coords, const float* feats, int64_t nMax,
+                      const uint32_t* nDev, int16_t* argmax, uint32_t* segTicket, hipStream_t s);
+
+}  // namespace mrirt

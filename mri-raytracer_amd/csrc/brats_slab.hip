@@ -235,7 +235,7 @@ static int launch_slab_t(const K1Args& a, hipStream_t s) {
     return MRIRT_OK;
 }
 
-// brats_march.hip calls this for: VGA layout, one modality, no overlays, no skipping, 64-thread workgroups
+// (brats_host.h) brats_march.hip calls this for: VGA layout, one modality, no overlays, no skipping, 64-thread workgroups
 int launch_slab_march(const K1Args& a, bool strict, bool shade, hipStream_t s) {
     if (a.map.blockPx != 8) return MRIRT_ERR_ARG;
     if (strict) return shade ? launch_slab_t<true, true>(a, s) : launch_slab_t<true, false>(a, s);

@@ -5,6 +5,7 @@
 // (inr/viewer/brats_viewer.py:219-230) is where a caller converts a linear grid once per case;
 // tiles/de-tiling have no reference counterpart (single device) — SURVEY.md section 8e.
 #include "mrirt_host.h"
+#include "skip_map.h"
 
 namespace mrirt {
 
@@ -148,7 +149,7 @@ __global__ __launch_bounds__(256) void bc4_decode_kernel(const uint2* __restrict
     }
 }
 
-// Macro-cell summaries for exact empty-space skipping (brats_march.hip): macro cell m covers the voxels
+// Macro-cell summaries for exact empty-space skipping (brats_skip.hip, skip_map.h): macro cell m covers the voxels
 // [8m, 8m+8] per axis (inclusive, so every trilinear cell whose base index lies in [8m, 8m+7] is inside).
 // ub = max + 2e-6 max|v|: three nested unfused lerps exceed the largest corner by at most ~12 ulp of the
 // largest magnitude; 2e-6 is twice that.  A NaN voxel makes the bound +inf (never skipped).

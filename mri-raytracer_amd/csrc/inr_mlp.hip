@@ -1704,8 +1704,8 @@ static int fill_args(const MrirtInrDesc* d, InrArgs& a) {
     return MRIRT_OK;
 }
 
-// Internal (mrirt_host.h): the forward pass with the point count read from device memory — used by the
-// chunked C5 render (brats_march.hip), whose producer kernel sizes each chunk's batch on the device.
+// Internal (brats_host.h): the forward pass with the point count read from device memory — used by the
+// chunked C5 render (brats_c5.hip), whose producer kernel sizes each chunk's batch on the device.
 int inr_forward_dev_n(const MrirtInrDesc* desc, const float* coords, const float* feats, int64_t nMax,
                       const uint32_t* nDev, int16_t* argmax, uint32_t* segTicket, hipStream_t s) {
     InrArgs a;

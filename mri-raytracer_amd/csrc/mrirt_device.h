@@ -407,12 +407,6 @@ __device__ __forceinline__ void store_rgba(void* out, int64_t idx, float r, floa
     }
 }
 
-// Exact empty-space skipping: the scratch MrirtSkip::mask points at (mrirt_skip_mask_words 32-bit words) holds the macro
-// cells' bits as whole 64-lane ballots, then two byte maps of skip_map_stride(cells) bytes each (the empty-radius map, and
-// the scratch of its separable passes).
-MRIRT_HD uint32_t skip_bit_words(uint32_t cells) { return ((cells + 63u) / 64u) * 2u; }
-MRIRT_HD uint32_t skip_map_stride(uint32_t cells) { return (cells + 3u) & ~3u; }
-
 __device__ __forceinline__ void wave_count_add(uint64_t* counter, uint32_t v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);

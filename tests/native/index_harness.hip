@@ -1,8 +1,9 @@
 // CPU sanitizer harness for the index arithmetic of the K1 march (test infrastructure; built by tests/test_index_sanitizers.py
 // with `hipcc --offload-host-only -fsanitize=address,undefined`: GPU sanitizers are not available on the pool).
 //
-// It includes the LIBRARY'S OWN sources, so prepare(), the pixel map, the cell -> element arithmetic of every layout, the
-// skipping pre-pass and MapWindow's index functions are the product's (MRIRT_HD functions, csrc/mrirt_device.h), not a copy.
+// It includes the LIBRARY'S OWN headers and links its host-compiled sources, so prepare() (csrc/brats_host.h), the pixel map and
+// the cell -> element arithmetic of every layout (MRIRT_HD functions, csrc/mrirt_device.h), the skipping pre-pass' and
+// MapWindow's index functions (csrc/skip_map.h) are the product's, not a copy.
 // What is walked, against buffers of exactly the sizes the host wrappers allocate (render.py `need`, mrirt_skip_mask_words):
 //   A. every element a sample's gathers can address, for every base cell sampleLinear's clamp allows (ix <= X - 2) and every
 //      voxel sampleLabel's clamp allows, in LINEAR / BRICK / VG / QUAD / VGA / LABCELL — exhaustively on small grids, on the
@@ -16,7 +17,8 @@
 //   D. the host half of mrirt_render_brats_skip / _ex for the launch of VERDICT r3 #1 (n = 72, QUAD, 3 channels, 160^2,
 //      both showSeg values) and random argument blocks (no device here: the launches themselves fail with a status).
 // Exit status 0 = no check failed (the sanitizers abort on their own findings).
-#include "../../mri-raytracer_amd/csrc/brats_march.hip"
+#include "../../mri-raytracer_amd/csrc/brats_host.h"
+#include "../../mri-raytracer_amd/csrc/skip_map.h"
 
 #include <algorithm>
 #include <cstdio>

@@ -1,13 +1,13 @@
 """The index arithmetic of the K1 march on the CPU under AddressSanitizer + UBSan (VERDICT r3 #1b).
 
 GPU sanitizers are not available on the pool, so the part of the kernels that can fault — which element, byte, pixel or map
-cell an id turns into — is compiled for the host as well (``MRIRT_HD`` functions in csrc/mrirt_device.h / brats_march.hip) and
+cell an id turns into — is compiled for the host as well (``MRIRT_HD`` functions in csrc/mrirt_device.h / skip_map.h) and
 ``tests/native/index_harness.hip`` walks it against buffers of exactly the sizes the host wrappers allocate: every tap of every
 layout for every admissible base cell, the workgroup/lane -> pixel map of frames and tile shards, the skipping pre-pass with
 its ballot words and byte maps, MapWindow's window moves, and the host halves of ``mrirt_render_brats_skip`` / ``_ex`` for the
 launch whose synchronisation aborted once in round 3 (72^3, QUAD, 3 channels, 160^2, both showSeg values).  The harness
-includes the library's sources themselves (host-only compile: ``hipcc --offload-host-only``), so it checks the product's
-code, not a copy."""
+includes the library's headers (csrc/brats_host.h, csrc/skip_map.h) and links the library's own sources, compiled host-only
+(``hipcc --offload-host-only``) under the same sanitizers, so it checks the product's code, not a copy."""
 import os
 import pathlib
 import shutil
@@ -25,8 +25,9 @@ SAN = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-g", 
 def build_harness() -> pathlib.Path:
     OUT.mkdir(parents=True, exist_ok=True)
     exe = OUT / "index_harness"
-    srcs = [ROOT / "tests" / "native" / "index_harness.hip"] + [CSRC / s for s in ("brats_slab.hip", "brats_ring.hip", "grid_ops.hip", "inr_mlp.hip")]
-    deps = srcs + list(CSRC.glob("*.h")) + [CSRC / "brats_march.hip", ROOT / "include" / "mrirt.h"]
+    srcs = [ROOT / "tests" / "native" / "index_harness.hip"] + [
+        CSRC / s for s in ("brats_march.hip", "brats_skip.hip", "brats_c5.hip", "brats_slab.hip", "brats_ring.hip", "grid_ops.hip", "inr_mlp.hip")]
+    deps = srcs + list(CSRC.glob("*.h")) + [ROOT / "include" / "mrirt.h"]
     if exe.exists() and exe.stat().st_mtime >= max(p.stat().st_mtime for p in deps):
         return exe
     objs = []

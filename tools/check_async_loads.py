@@ -326,28 +326,31 @@ def llvm_bin() -> pathlib.Path:
                        + ", ".join(str(c) for c in cands) + " — set MRIRT_LLVM_BIN to the directory that holds them")
 
 
-def device_disassembly(so: pathlib.Path) -> str:
-    """gfx950 disassembly of every code object embedded in the library: the .hip_fatbin section holds one offload bundle per
-    HIP source; each is unbundled and disassembled."""
-    import tempfile
+def code_objects(so: pathlib.Path, td: pathlib.Path):
+    """The gfx950 code objects embedded in the library, unbundled into the directory td: the .hip_fatbin section holds one
+    offload bundle per HIP source."""
     LLVM = llvm_bin()
-    out = []
+    fat = td / "fatbin.bin"
+    subprocess.run([str(LLVM / "llvm-objcopy"), "-O", "binary", "--only-section=.hip_fatbin", str(so), str(fat)], check=True)
+    blob = fat.read_bytes()
+    starts = [m.start() for m in re.finditer(re.escape(MAGIC), blob)]
+    for i, st in enumerate(starts):
+        chunk = td / f"bundle{i}.bin"
+        chunk.write_bytes(blob[st:starts[i + 1] if i + 1 < len(starts) else len(blob)])
+        co = td / f"dev{i}.co"
+        r = subprocess.run([str(LLVM / "clang-offload-bundler"), "--unbundle", "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950",
+                            f"--input={chunk}", f"--output={co}"], capture_output=True, text=True)
+        if r.returncode == 0 and co.exists() and co.stat().st_size != 0:
+            yield co
+
+
+def device_disassembly(so: pathlib.Path) -> str:
+    """gfx950 disassembly of every code object embedded in the library."""
+    import tempfile
+    objdump = str(llvm_bin() / "llvm-objdump")
     with tempfile.TemporaryDirectory() as td:
-        td = pathlib.Path(td)
-        fat = td / "fatbin.bin"
-        subprocess.run([str(LLVM / "llvm-objcopy"), "-O", "binary", "--only-section=.hip_fatbin", str(so), str(fat)], check=True)
-        blob = fat.read_bytes()
-        starts = [m.start() for m in re.finditer(re.escape(MAGIC), blob)]
-        for i, st in enumerate(starts):
-            chunk = td / f"bundle{i}.bin"
-            chunk.write_bytes(blob[st:starts[i + 1] if i + 1 < len(starts) else len(blob)])
-            co = td / f"dev{i}.co"
-            r = subprocess.run([str(LLVM / "clang-offload-bundler"), "--unbundle", "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950",
-                                f"--input={chunk}", f"--output={co}"], capture_output=True, text=True)
-            if r.returncode != 0 or not co.exists() or co.stat().st_size == 0:
-                continue
-            out.append(subprocess.run([str(LLVM / "llvm-objdump"), "-d", str(co)], capture_output=True, text=True).stdout)
-    return "\n".join(out)
+        return "\n".join(subprocess.run([objdump, "-d", str(co)], capture_output=True, text=True).stdout
+                         for co in code_objects(so, pathlib.Path(td)))
 
 
 def main():
