@@ -4,6 +4,8 @@
 // Reference counterparts: the upload `create_buffer + copy_from_numpy`
 // (inr/viewer/brats_viewer.py:219-230) is where a caller converts a linear grid once per case;
 // tiles/de-tiling have no reference counterpart (single device) — SURVEY.md section 8e.
+#include <float.h>
+
 #include "mrirt_host.h"
 #include "skip_map.h"
 
@@ -152,14 +154,15 @@ __global__ __launch_bounds__(256) void bc4_decode_kernel(const uint2* __restrict
 // Macro-cell summaries for exact empty-space skipping (brats_skip.hip, skip_map.h): macro cell m covers the voxels
 // [8m, 8m+8] per axis (inclusive, so every trilinear cell whose base index lies in [8m, 8m+7] is inside).
 // ub = max + 2e-6 max|v|: three nested unfused lerps exceed the largest corner by at most ~12 ulp of the
-// largest magnitude; 2e-6 is twice that.  A NaN voxel makes the bound +inf (never skipped).
+// largest magnitude; 2e-6 is twice that.  A NaN voxel makes the bound +inf (never skipped), and so does a cell whose
+// max - min is not below FLT_MAX / 2: the lerps themselves can overflow there (-3e38 + t (3e38 - -3e38) = +inf).
 __global__ __launch_bounds__(256) void macro_max_kernel(const float* __restrict__ lin, float* __restrict__ ub,
                                                         uint32_t X, uint32_t Y, uint32_t Z, uint32_t mx, uint32_t my, uint32_t cells) {
     const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= cells) return;
     const uint32_t cx = c % mx, cy = (c / mx) % my, cz = c / (mx * my);
     const uint32_t x1 = min(8 * cx + 8, X - 1), y1 = min(8 * cy + 8, Y - 1), z1 = min(8 * cz + 8, Z - 1);
-    float vmax = -INFINITY, amax = 0.0f;
+    float vmax = -INFINITY, vmin = INFINITY, amax = 0.0f;
     bool nan = false;
     for (uint32_t z = 8 * cz; z <= z1; ++z)
         for (uint32_t y = 8 * cy; y <= y1; ++y)
@@ -167,9 +170,13 @@ __global__ __launch_bounds__(256) void macro_max_kernel(const float* __restrict_
                 const float v = lin[x + (size_t)X * (y + (size_t)Y * z)];
                 nan |= v != v;
                 vmax = fmaxf(vmax, v);
+                vmin = fminf(vmin, v);
                 amax = fmaxf(amax, fabsf(v));
             }
-    ub[c] = nan ? INFINITY : vmax + 2e-6f * amax;
+    // a value range of FLT_MAX: lerp's b - a overflows, and a + t inf is +inf between two finite voxels.  Half of that is
+    // the limit: the inner lerps may leave [vmin, vmax] by ulps before the outer ones subtract them
+    const bool wide = !(vmax - vmin < 0.5f * FLT_MAX);
+    ub[c] = nan || wide ? INFINITY : vmax + 2e-6f * amax;
 }
 
 __global__ __launch_bounds__(256) void macro_label_kernel(const uint32_t* __restrict__ lin, uint32_t* __restrict__ any,
