@@ -30,7 +30,8 @@ extern "C" {
  *    mrirt_render_brats_inr); the packed INR image ends in 32 KiB of slack more (mrirt_inr_pack_bytes says how much to allocate). */
 /*    Backward-compatible additions under the same version: MrirtMeshParams + mrirt_render_mesh (K4, the triangle-mesh BVH
  *    ray tracer), mrirt_sizeof(6); mrirt_edt_scratch_bytes, mrirt_edt_squared, mrirt_hausdorff (no new struct);
- *    mrirt_surface_scratch_bytes, mrirt_surface_count, mrirt_surface_extract (no new struct). */
+ *    mrirt_surface_scratch_bytes, mrirt_surface_count, mrirt_surface_extract (no new struct);
+ *    mrirt_render_brats_backward (the K1 backward pass on LINEAR grids; no new struct). */
 #define MRIRT_ABI_VERSION 4
 
 typedef enum MrirtStatus {
@@ -465,6 +466,31 @@ int mrirt_surface_count(const int16_t* labels, const uint32_t hwd[3], uint32_t c
 int mrirt_surface_extract(const int16_t* labels, const uint32_t hwd[3], uint32_t class_mask, const float spacing[3],
                           const float origin[3], float* verts, int64_t vert_cap, int32_t* tris, int64_t tri_cap,
                           void* scratch, int64_t scratch_bytes, int64_t* counts_dev, void* stream);
+
+/* ------------------------------------------------------------------------------------ */
+/* K1 backward: frame gradients to voxel grids and transfer-function parameters         */
+/* ------------------------------------------------------------------------------------ */
+/* For one K1 frame on LINEAR fp32 grids (whole image, shadeMode 0, either camera mode) with C[p] the RGB brats_main writes
+ * for pixel p, and an upstream G[p] = dL/dC[p] (grad_rgba: device fp32 RGBA, 16-byte aligned, grad_pitch_px pixels per row;
+ * the alpha channel is ignored: the shader writes the constant 1):
+ *   grad_vol[m][voxel] += dL/d vol[m][voxel]                   (LINEAR order, every enabled modality)
+ *   grad_tf[0..3]      += dL/d(ww, wl, intensityAlpha, gamma)  (device doubles)
+ * The function differentiated is the one the forward executed: ray set-up, t0 / t1, the sample positions, their cells and
+ * trilinear weights are constants (the forward's own fp32 values), and so are the steps taken: the `t < t1 && T > ert`
+ * decisions come from re-marching in the forward's STRICT arithmetic (early ray termination is a discrete decision and
+ * carries no gradient).  Label overlays (showSeg, showPred) are fixed occluders: they enter T and the colour behind a
+ * sample but receive no gradient.  Not differentiated: camera, stepSize, volWeight, the LUT.  The per-sample chain is
+ * written out in csrc/brats_grad.h; its arithmetic is fp64, the voxel sums are float atomic adds (their order, hence
+ * the last bits, varies from run to run).  ww must not be 0.
+ * Accumulates (+=): the caller zeroes, or keeps summing over views.  grad_vol (or grad_vol[m]) may be NULL for a modality that
+ * is disabled or whose gradient is not wanted (a disabled modality's buffer is never touched); grad_tf may be NULL.
+ * Checks (before any HIP call): those of every K1 entry point, and
+ *   MRIRT_ERR_LAYOUT  ext->layout or ext->labelLayout other than MRIRT_LAYOUT_LINEAR
+ *   MRIRT_ERR_ARG     shadeMode != 0, tile sharding, outFormat != MRIRT_OUT_RGBA32F, math != MRIRT_MATH_STRICT */
+int mrirt_render_brats_backward(const MrirtBratsParams* params, const MrirtRenderExt* ext,
+                                const float* const vol[4], const uint32_t* labels, const uint32_t* preds,
+                                const float* grad_rgba, int64_t grad_pitch_px,
+                                float* const grad_vol[4], double* grad_tf, void* stream);
 
 /* ------------------------------------------------------------------------------------ */
 /* Per-sample INR render, one call (BASELINE config 5)                                   */

@@ -5,6 +5,7 @@ the task-mandated name ``mri-raytracer_amd``.  Layout:
   csrc/       hand-written gfx950 HIP kernels + the C ABI (include/mrirt.h) -> libmrirt.so
   _lib.py     ctypes binding (fails loudly when the library is missing — no CPU fallback)
   render.py   render_brats / render_volume_u8 / render_sdf over device tensors
+  grad.py     K1 backward: render_brats_backward, render_brats_autograd (frame gradients to voxels and window / level)
   mesh.py     K4: PLY loading, the reference's BVH, upload + validation, render_mesh; class surfaces of label volumes
   shim.py     slangpy-shaped ``Device`` / ``ComputeKernel.dispatch(thread_count, vars, ...)``
   camera.py   OrbitalCamera (both reference variants)
@@ -13,8 +14,9 @@ the task-mandated name ``mri-raytracer_amd``.  Layout:
   tiles.py    image-tile sharding + RCCL framebuffer gather (one process per GPU)
   synth.py    deterministic synthetic scenes for tests and bench
 """
-from . import _lib, camera, inr, mesh, nifti, params, render, shim, synth, tiles, torch_ops, viewer, volume  # noqa: F401
+from . import _lib, camera, grad, inr, mesh, nifti, params, render, shim, synth, tiles, torch_ops, viewer, volume  # noqa: F401
 from .camera import OrbitalCamera  # noqa: F401
+from .grad import render_brats_autograd, render_brats_backward  # noqa: F401
 from .inr import apply_mlp, build_input, inr_forward, model_load, predict_volume, render_brats_inr  # noqa: F401
 from .mesh import (build_bvh, extract_surface, load_ply, normalize_mesh, render_mesh, surface_mesh,  # noqa: F401
                    upload_mesh)

@@ -16,7 +16,7 @@ PKG_DIR = pathlib.Path(__file__).resolve().parent
 CSRC = PKG_DIR / "csrc"
 INCLUDE = PKG_DIR.parent / "include"
 SO_PATH = pathlib.Path(os.environ.get("MRIRT_LIB", PKG_DIR / "libmrirt.so"))   # override: A/B builds in development
-HIP_SOURCES = ["brats_march.hip", "brats_skip.hip", "brats_c5.hip", "brats_slab.hip", "brats_ring.hip", "volume_march.hip", "grid_ops.hip", "inr_mlp.hip",
+HIP_SOURCES = ["brats_march.hip", "brats_skip.hip", "brats_c5.hip", "brats_slab.hip", "brats_ring.hip", "brats_backward.hip", "volume_march.hip", "grid_ops.hip", "inr_mlp.hip",
                "mesh_rt.hip", "edt.hip", "surface.hip", "abort_trace.cpp"]
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17", "-Wall"]
 
@@ -31,6 +31,7 @@ ABI_SYMBOLS = [
     "mrirt_sizeof", "mrirt_brats_skip_applicable", "mrirt_brats_kernel_family", "mrirt_install_abort_trace",
     "mrirt_edt_scratch_bytes", "mrirt_edt_squared", "mrirt_hausdorff",
     "mrirt_surface_scratch_bytes", "mrirt_surface_count", "mrirt_surface_extract",
+    "mrirt_render_brats_backward",
 ]
 
 ABI_VERSION = 4          # MRIRT_ABI_VERSION of include/mrirt.h this binding was written against
@@ -320,6 +321,8 @@ def lib() -> C.CDLL:
     l.mrirt_surface_count.restype = i32
     l.mrirt_surface_extract.argtypes = [vp, C.POINTER(u32), u32, C.POINTER(f32), C.POINTER(f32), vp, i64, vp, i64, vp, i64, vp, vp]
     l.mrirt_surface_extract.restype = i32
+    l.mrirt_render_brats_backward.argtypes = [C.POINTER(BratsParams), C.POINTER(RenderExt), C.POINTER(vp), vp, vp, vp, i64, C.POINTER(vp), vp, vp]
+    l.mrirt_render_brats_backward.restype = i32
     l.mrirt_status_string.argtypes = [i32]
     l.mrirt_status_string.restype = C.c_char_p
     l.mrirt_sizeof.argtypes = [u32]

@@ -111,6 +111,52 @@ Tensor render_brats(const Tensor& params, const Tensor& ext, const OptTensor& vo
     return out;
 }
 
+// gradients of one K1 frame on LINEAR fp32 grids through mrirt_render_brats_backward: dL/dvol0..3 (an empty tensor for a modality
+// that is disabled or not bound; an empty tensor also stands for an absent modality on the way in) and dL/d(ww, wl,
+// intensityAlpha, gamma) as float64 [4]; freshly zeroed outputs
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> render_brats_backward(const Tensor& params, const Tensor& ext, const Tensor& grad_out,
+                                                                         const OptTensor& vol0, const OptTensor& vol1, const OptTensor& vol2,
+                                                                         const OptTensor& vol3, const OptTensor& labels, const OptTensor& preds) {
+    const MrirtBratsParams P = unblob<MrirtBratsParams>(params, "MrirtBratsParams");
+    const MrirtRenderExt E = unblob<MrirtRenderExt>(ext, "MrirtRenderExt");
+    const auto present = [](const OptTensor& t) { return t.has_value() && t->numel() != 0 ? t : OptTensor(); };
+    const OptTensor vols[4] = { present(vol0), present(vol1), present(vol2), present(vol3) };
+    const OptTensor lab = present(labels), prd = present(preds);
+    const char* names[4] = { "gIntensity0", "gIntensity1", "gIntensity2", "gIntensity3" };
+    const int64_t nvox = (int64_t)P.dims[0] * P.dims[1] * P.dims[2];
+    const int64_t W = P.imageSize[0], H = P.imageSize[1];
+    std::optional<at::Device> dev;
+    const float* g = static_cast<const float*>(dev_ptr(grad_out, at::kFloat, "grad_out"));
+    same_device(dev, grad_out, "grad_out");
+    TORCH_CHECK_VALUE(grad_out.dim() == 3 && grad_out.size(0) == H && grad_out.size(1) == W && grad_out.size(2) == 4,
+                      "grad_out: expected (", H, ", ", W, ", 4)");
+    const float* vp[4];
+    for (int m = 0; m < 4; ++m) {
+        vp[m] = static_cast<const float*>(dev_ptr(vols[m], at::kFloat, names[m]));
+        same_device(dev, vols[m], names[m]);
+        TORCH_CHECK_VALUE(P.volEnabled[m] == 0 || (vols[m].has_value() && vols[m]->numel() >= nvox),
+                          names[m], " is enabled but holds fewer than ", nvox, " elements");
+    }
+    const uint32_t* lp = static_cast<const uint32_t*>(dev_ptr(lab, at::kInt, "gLabels"));
+    const uint32_t* pp = static_cast<const uint32_t*>(dev_ptr(prd, at::kInt, "gPreds"));
+    TORCH_CHECK_VALUE(P.showSeg == 0 || (lab.has_value() && lab->numel() >= nvox), "showSeg is set but gLabels is missing or too small");
+    TORCH_CHECK_VALUE(P.showPred == 0 || (prd.has_value() && prd->numel() >= nvox), "showPred is set but gPreds is missing or too small");
+    same_device(dev, lab, "gLabels");
+    same_device(dev, prd, "gPreds");
+    DeviceGuard guard(*dev);
+    Tensor gv[4];
+    float* gp[4];
+    for (int m = 0; m < 4; ++m) {
+        const bool on = P.volEnabled[m] != 0 && vols[m].has_value();
+        gv[m] = at::zeros({ on ? nvox : 0 }, at::TensorOptions().dtype(at::kFloat).device(*dev));
+        gp[m] = on ? gv[m].data_ptr<float>() : nullptr;
+    }
+    Tensor gtf = at::zeros({ 4 }, at::TensorOptions().dtype(at::kDouble).device(*dev));
+    check(mrirt_render_brats_backward(&P, &E, vp, lp, pp, g, W, gp, gtf.data_ptr<double>(), current_stream()),
+          "mrirt_render_brats_backward");
+    return { gv[0], gv[1], gv[2], gv[3], gtf };
+}
+
 // volume_cs (scripts/volumeRendering/volume_render.slang:104-148) through mrirt_render_volume
 Tensor render_volume(const Tensor& params, const Tensor& ext, const Tensor& volume, int64_t mode) {
     const MrirtVolumeParams P = unblob<MrirtVolumeParams>(params, "MrirtVolumeParams");
@@ -300,6 +346,8 @@ std::tuple<Tensor, Tensor> surface_extract(const Tensor& labels, int64_t class_m
 
 TORCH_LIBRARY(mrirt_native, m) {
     m.def("render_brats(Tensor params, Tensor ext, Tensor? vol0, Tensor? vol1, Tensor? vol2, Tensor? vol3, Tensor? labels, Tensor? preds) -> Tensor");
+    m.def("render_brats_backward(Tensor params, Tensor ext, Tensor grad_out, Tensor? vol0, Tensor? vol1, Tensor? vol2, Tensor? vol3, "
+          "Tensor? labels, Tensor? preds) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
     m.def("render_volume(Tensor params, Tensor ext, Tensor volume, int mode) -> Tensor");
     m.def("render_sdf(Tensor params, int width, int height, Tensor like) -> Tensor");
     m.def("render_mesh(Tensor params, Tensor ext, Tensor nodes, Tensor tris, Tensor verts, int max_depth) -> Tensor");
@@ -315,6 +363,7 @@ TORCH_LIBRARY(mrirt_native, m) {
 // implementations are registered for every backend and check their arguments themselves
 TORCH_LIBRARY_IMPL(mrirt_native, CompositeExplicitAutograd, m) {
     m.impl("render_brats", &render_brats);
+    m.impl("render_brats_backward", &render_brats_backward);
     m.impl("render_volume", &render_volume);
     m.impl("render_sdf", &render_sdf);
     m.impl("render_mesh", &render_mesh);

@@ -170,6 +170,59 @@ def _(params, ext, vol0, vol1, vol2, vol3, labels, preds):
     return torch.empty(_out_shape(int(P.imageSize[0]), int(P.imageSize[1]), E), dtype=dt, device=dev)
 
 
+# --- K1 backward --------------------------------------------------------------------------------
+def _present(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    return None if t is None or t.numel() == 0 else t
+
+
+@torch.library.custom_op("mrirt::render_brats_backward", mutates_args=())
+def render_brats_backward(params: torch.Tensor, ext: torch.Tensor, grad_out: torch.Tensor, vol0: Optional[torch.Tensor],
+                          vol1: Optional[torch.Tensor], vol2: Optional[torch.Tensor], vol3: Optional[torch.Tensor],
+                          labels: Optional[torch.Tensor], preds: Optional[torch.Tensor]
+                          ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Gradients of one K1 frame on LINEAR fp32 grids through mrirt_render_brats_backward: ``grad_out`` is dL/dframe, fp32
+    [H, W, 4] (alpha ignored).  Returns dL/dvol0..3 (fp32 [X*Y*Z]; an empty tensor for a modality that is disabled or not
+    bound — an empty tensor also stands for an absent modality on the way in) and dL/d(ww, wl, intensityAlpha, gamma) as
+    float64 [4].  Freshly zeroed outputs: summing over views is the caller's ``+=``."""
+    P, E = _unblob(params, _lib.BratsParams), _unblob(ext, _lib.RenderExt)
+    dims = [int(v) for v in P.dims]
+    nvox = dims[0] * dims[1] * dims[2]
+    W, H = int(P.imageSize[0]), int(P.imageSize[1])
+    vols = [_dev_flat(_present(v), torch.float32, f"gIntensity{m}") for m, v in enumerate((vol0, vol1, vol2, vol3))]
+    lab = _dev_flat(_present(labels), torch.int32, "gLabels")
+    prd = _dev_flat(_present(preds), torch.int32, "gPreds")
+    g = _dev_flat(grad_out, torch.float32, "grad_out")
+    if tuple(g.shape) != (H, W, 4):
+        raise ValueError(f"grad_out: expected ({H}, {W}, 4), got {tuple(g.shape)}")
+    for m, v in enumerate(vols):
+        if P.volEnabled[m] != 0 and (v is None or v.numel() < nvox):
+            raise ValueError(f"gIntensity{m} is enabled but holds {0 if v is None else v.numel()} < {nvox} elements")
+    if P.showSeg != 0 and (lab is None or lab.numel() < nvox):
+        raise ValueError("showSeg is set but gLabels is missing or too small")
+    if P.showPred != 0 and (prd is None or prd.numel() < nvox):
+        raise ValueError("showPred is set but gPreds is missing or too small")
+    dev = _one_device([("grad_out", g)] + [(f"gIntensity{m}", v) for m, v in enumerate(vols)] + [("gLabels", lab), ("gPreds", prd)])
+    vp = (C.c_void_p * 4)(*[C.c_void_p(v.data_ptr()) if v is not None else None for v in vols])
+    with torch.cuda.device(dev):
+        gv = [torch.zeros(nvox if (P.volEnabled[m] != 0 and vols[m] is not None) else 0, dtype=torch.float32, device=dev)
+              for m in range(4)]
+        gtf = torch.zeros(4, dtype=torch.float64, device=dev)
+        gp = (C.c_void_p * 4)(*[C.c_void_p(t.data_ptr()) if t.numel() else None for t in gv])
+        rc = _lib.lib().mrirt_render_brats_backward(C.byref(P), C.byref(E), vp, _ptr(lab), _ptr(prd), _ptr(g), W, gp, _ptr(gtf),
+                                                    _stream())
+    _lib.check(rc, "mrirt_render_brats_backward")
+    return gv[0], gv[1], gv[2], gv[3], gtf
+
+
+@render_brats_backward.register_fake
+def _(params, ext, grad_out, vol0, vol1, vol2, vol3, labels, preds):
+    P = _unblob(params, _lib.BratsParams)
+    nvox = int(P.dims[0]) * int(P.dims[1]) * int(P.dims[2])
+    gv = [torch.empty(nvox if (P.volEnabled[m] != 0 and v is not None and v.numel() != 0) else 0, dtype=torch.float32,
+                      device=grad_out.device) for m, v in enumerate((vol0, vol1, vol2, vol3))]
+    return gv[0], gv[1], gv[2], gv[3], torch.empty(4, dtype=torch.float64, device=grad_out.device)
+
+
 # --- K2 -----------------------------------------------------------------------------------------
 _VOX_DTYPE = {_lib.VOX_U32X4: torch.int32, _lib.VOX_U8: torch.uint8, _lib.VOX_F32: torch.float32}
 
