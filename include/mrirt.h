@@ -412,6 +412,35 @@ int mrirt_inr_predict_volume(const MrirtInrDesc* desc, const float* mods, const 
                              int16_t* pred, void* stream);
 
 /* ------------------------------------------------------------------------------------ */
+/* INR training step (inr/inr/model.py:57-90 make_loss_and_grad): fp32, ReLU kinds only  */
+/* ------------------------------------------------------------------------------------ */
+/* One step is forward_f32 -> loss -> backward on one stream with one scratch buffer.  The network is its fp32 master copy:
+ * w_f32 row-major [in][out] per layer, layers concatenated unpadded (what mrirt_inr_pack_weights takes), b_f32 the biases
+ * concatenated UNPADDED; grad_w / grad_b have the same two layouts.  desc->weights / desc->biases are not read.  Kinds
+ * MRIRT_INR_FOURIER_RELU and MRIRT_INR_RAW_RELU over every shape mrirt_inr_pack_bytes accepts; the SIREN kinds are refused
+ * (MRIRT_ERR_ARG).  1 <= n < 2^31.  Products and sums are fp32 (v_mfma_f32_16x16x4_f32, a k-ordered fma chain); every sum over
+ * the batch runs in a fixed order (no float atomics): the same inputs give the same bits.  No host synchronisation.
+ * scratch: device memory, 16-byte aligned, owned by the caller; 0 bytes = unsupported kind / shape / n. */
+int64_t mrirt_inr_train_scratch_bytes(const MrirtInrDesc* desc, int64_t n);
+/* what the loss alone needs (the first bytes of the step's scratch: the three calls may share one buffer) */
+int64_t mrirt_inr_loss_scratch_bytes(int64_t n);
+/* logits[n][outDim] = the network on coords[n][3] / feats[n][numMods] (RAW kind: feats[n][inDim], coords unused); leaves
+ * the input matrix and every hidden activation in scratch for the backward pass */
+int mrirt_inr_forward_f32(const MrirtInrDesc* desc, const float* w_f32, const float* b_f32, const float* coords,
+                          const float* feats, int64_t n, float* logits, void* scratch, int64_t scratch_bytes, void* stream);
+/* loss[1] = (1 - dw) ce + dw (1 - mean_k dice_k) for dw > 0, else ce, with ce = mean_p(ce_p cw[label_p]) and
+ * dice_k = (2 sum_p p_pk y_pk + 1e-6) / (sum_p p_pk + sum_p y_pk + 1e-6); aux[2 C] = ce per class (sum_p ce_p y_pk /
+ * max(count_k, 1)), then dice per class; dlogits[n][C] = dloss/dlogits (NULL: not computed).  labels int32 in 0..C-1 (a
+ * label outside it reads no memory; it counts for no class and weighs 0).  class_weights: C floats on the HOST.
+ * 1 <= num_classes <= 16, dice_weight finite.  The class sums are fp64.  loss and aux stay on the device. */
+int mrirt_inr_loss(const float* logits, const int32_t* labels, int64_t n, uint32_t num_classes, const float* class_weights,
+                   float dice_weight, float* loss, float* aux, float* dlogits, void* scratch, int64_t scratch_bytes, void* stream);
+/* grad_w / grad_b (+= with flags bit 0, else =) from dlogits[n][outDim] and what forward_f32 left in the same scratch for
+ * the same desc and n: dW_l = h_{l-1}^T dz_l, db_l = sum_p dz_l, dz_{l-1} = (dz_l W_l^T) where z_{l-1} > 0, else 0. */
+int mrirt_inr_backward(const MrirtInrDesc* desc, const float* w_f32, int64_t n, const float* dlogits, float* grad_w,
+                       float* grad_b, uint32_t flags, void* scratch, int64_t scratch_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------ */
 /* Exact distance transform and Hausdorff distance (inr/inr/model.py:164-195)            */
 /* ------------------------------------------------------------------------------------ */
 /* labels / pred / truth: the int16 [H][W][D] C-order volume mrirt_inr_predict_volume writes (device).  The coordinate of

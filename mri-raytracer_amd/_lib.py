@@ -17,7 +17,7 @@ CSRC = PKG_DIR / "csrc"
 INCLUDE = PKG_DIR.parent / "include"
 SO_PATH = pathlib.Path(os.environ.get("MRIRT_LIB", PKG_DIR / "libmrirt.so"))   # override: A/B builds in development
 HIP_SOURCES = ["brats_march.hip", "brats_skip.hip", "brats_c5.hip", "brats_slab.hip", "brats_ring.hip", "brats_backward.hip", "volume_march.hip", "grid_ops.hip", "inr_mlp.hip",
-               "mesh_rt.hip", "edt.hip", "surface.hip", "abort_trace.cpp"]
+               "inr_train.hip", "mesh_rt.hip", "edt.hip", "surface.hip", "abort_trace.cpp"]
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17", "-Wall"]
 
 # every extern "C" symbol include/mrirt.h declares
@@ -32,6 +32,7 @@ ABI_SYMBOLS = [
     "mrirt_edt_scratch_bytes", "mrirt_edt_squared", "mrirt_hausdorff",
     "mrirt_surface_scratch_bytes", "mrirt_surface_count", "mrirt_surface_extract",
     "mrirt_render_brats_backward",
+    "mrirt_inr_train_scratch_bytes", "mrirt_inr_loss_scratch_bytes", "mrirt_inr_forward_f32", "mrirt_inr_loss", "mrirt_inr_backward",
 ]
 
 ABI_VERSION = 4          # MRIRT_ABI_VERSION of include/mrirt.h this binding was written against
@@ -323,6 +324,16 @@ def lib() -> C.CDLL:
     l.mrirt_surface_extract.restype = i32
     l.mrirt_render_brats_backward.argtypes = [C.POINTER(BratsParams), C.POINTER(RenderExt), C.POINTER(vp), vp, vp, vp, i64, C.POINTER(vp), vp, vp]
     l.mrirt_render_brats_backward.restype = i32
+    l.mrirt_inr_train_scratch_bytes.argtypes = [C.POINTER(InrDesc), i64]
+    l.mrirt_inr_train_scratch_bytes.restype = i64
+    l.mrirt_inr_loss_scratch_bytes.argtypes = [i64]
+    l.mrirt_inr_loss_scratch_bytes.restype = i64
+    l.mrirt_inr_forward_f32.argtypes = [C.POINTER(InrDesc), vp, vp, vp, vp, i64, vp, vp, i64, vp]
+    l.mrirt_inr_forward_f32.restype = i32
+    l.mrirt_inr_loss.argtypes = [vp, vp, i64, u32, C.POINTER(f32), f32, vp, vp, vp, vp, i64, vp]
+    l.mrirt_inr_loss.restype = i32
+    l.mrirt_inr_backward.argtypes = [C.POINTER(InrDesc), vp, i64, vp, vp, vp, u32, vp, i64, vp]
+    l.mrirt_inr_backward.restype = i32
     l.mrirt_status_string.argtypes = [i32]
     l.mrirt_status_string.restype = C.c_char_p
     l.mrirt_sizeof.argtypes = [u32]

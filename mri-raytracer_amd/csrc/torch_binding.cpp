@@ -241,6 +241,88 @@ Tensor inr_forward(const Tensor& weights, const Tensor& biases, int64_t kind, in
     return out;
 }
 
+// ---- INR training step (fp32): mrirt_inr_forward_f32 / mrirt_inr_loss / mrirt_inr_backward ----
+struct TrainShape { MrirtInrDesc d; int64_t bytes, nw, nb; };
+
+TrainShape train_shape(int64_t kind, int64_t num_layers, int64_t in_dim, int64_t out_dim, int64_t hidden, int64_t fourier_freqs,
+                       int64_t num_mods, int64_t n) {
+    TrainShape t;
+    std::memset(&t.d, 0, sizeof t.d);
+    t.d.kind = (uint32_t)kind; t.d.numLayers = (uint32_t)num_layers; t.d.inDim = (uint32_t)in_dim; t.d.outDim = (uint32_t)out_dim;
+    t.d.hidden = (uint32_t)hidden; t.d.fourierFreqs = (uint32_t)fourier_freqs; t.d.numMods = (uint32_t)num_mods;
+    t.bytes = mrirt_inr_train_scratch_bytes(&t.d, n);
+    TORCH_CHECK_VALUE(t.bytes > 0, "unsupported network kind / shape / n for the training step (ReLU kinds only)");
+    t.nw = in_dim * hidden + (num_layers - 2) * hidden * hidden + hidden * out_dim;
+    t.nb = (num_layers - 1) * hidden + out_dim;
+    return t;
+}
+
+// (logits [n, out_dim], scratch uint8): the fp32 forward that leaves its activations for inr_backward
+std::tuple<Tensor, Tensor> inr_forward_f32(const Tensor& weights, const Tensor& biases, int64_t kind, int64_t num_layers, int64_t in_dim,
+                                           int64_t out_dim, int64_t hidden, int64_t fourier_freqs, int64_t num_mods,
+                                           const OptTensor& coords, const OptTensor& feats, int64_t n) {
+    const TrainShape t = train_shape(kind, num_layers, in_dim, out_dim, hidden, fourier_freqs, num_mods, n);
+    const float* w = static_cast<const float*>(dev_ptr(weights, at::kFloat, "weights"));
+    const float* b = static_cast<const float*>(dev_ptr(biases, at::kFloat, "biases"));
+    TORCH_CHECK_VALUE(weights.numel() >= t.nw && biases.numel() >= t.nb, "weights / biases are smaller than the network (", t.nw, " / ", t.nb, " floats)");
+    const float* co = static_cast<const float*>(dev_ptr(coords, at::kFloat, "coords"));
+    const float* fe = static_cast<const float*>(dev_ptr(feats, at::kFloat, "feats"));
+    TORCH_CHECK_VALUE(kind >= 2 || (coords.has_value() && coords->numel() >= 3 * n), "coords must hold [n, 3] floats");
+    const int64_t width = kind >= 2 ? in_dim : num_mods;
+    TORCH_CHECK_VALUE(width == 0 || (feats.has_value() && feats->numel() >= width * n), "feats must hold [n, ", width, "] floats");
+    std::optional<at::Device> dev = weights.device();
+    same_device(dev, biases, "biases");
+    same_device(dev, coords, "coords");
+    same_device(dev, feats, "feats");
+    DeviceGuard guard(*dev);
+    Tensor out = at::empty({ n, out_dim }, at::TensorOptions().dtype(at::kFloat).device(*dev));
+    Tensor scratch = at::empty({ t.bytes }, at::TensorOptions().dtype(at::kByte).device(*dev));
+    check(mrirt_inr_forward_f32(&t.d, w, b, co, fe, n, out.data_ptr<float>(), scratch.data_ptr(), t.bytes, current_stream()),
+          "mrirt_inr_forward_f32");
+    return { out, scratch };
+}
+
+// (loss [1], aux [2, C], dlogits [n, C]) of the reference's loss (inr/inr/model.py:64-88) through mrirt_inr_loss
+std::tuple<Tensor, Tensor, Tensor> inr_loss(const Tensor& logits, const Tensor& labels, at::ArrayRef<double> class_weights, double dice_weight) {
+    const float* z = static_cast<const float*>(dev_ptr(logits, at::kFloat, "logits"));
+    const int32_t* lab = static_cast<const int32_t*>(dev_ptr(labels, at::kInt, "labels"));
+    TORCH_CHECK_VALUE(logits.dim() == 2 && logits.size(0) >= 1 && labels.numel() == logits.size(0), "logits must be [n, C] with n >= 1 and labels [n]");
+    const int64_t n = logits.size(0), nc = logits.size(1);
+    TORCH_CHECK_VALUE(nc >= 1 && nc <= 16 && (int64_t)class_weights.size() == nc, "1..16 classes, one class weight each");
+    float cw[16];
+    for (int64_t k = 0; k < nc; ++k) cw[k] = (float)class_weights[k];
+    std::optional<at::Device> dev = logits.device();
+    same_device(dev, labels, "labels");
+    DeviceGuard guard(*dev);
+    const int64_t nbytes = mrirt_inr_loss_scratch_bytes(n);
+    const auto f32 = at::TensorOptions().dtype(at::kFloat).device(*dev);
+    Tensor loss = at::empty({ 1 }, f32), aux = at::empty({ 2, nc }, f32), dl = at::empty_like(logits);
+    Tensor scratch = at::empty({ nbytes }, at::TensorOptions().dtype(at::kByte).device(*dev));
+    check(mrirt_inr_loss(z, lab, n, (uint32_t)nc, cw, (float)dice_weight, loss.data_ptr<float>(), aux.data_ptr<float>(), dl.data_ptr<float>(),
+                         scratch.data_ptr(), nbytes, current_stream()), "mrirt_inr_loss");
+    return { loss, aux, dl };
+}
+
+// (grad_w, grad_b) through mrirt_inr_backward from dlogits and the scratch inr_forward_f32 returned
+std::tuple<Tensor, Tensor> inr_backward(const Tensor& weights, const Tensor& dlogits, const Tensor& scratch, int64_t kind, int64_t num_layers,
+                                        int64_t in_dim, int64_t out_dim, int64_t hidden, int64_t fourier_freqs, int64_t num_mods, int64_t n) {
+    const TrainShape t = train_shape(kind, num_layers, in_dim, out_dim, hidden, fourier_freqs, num_mods, n);
+    const float* w = static_cast<const float*>(dev_ptr(weights, at::kFloat, "weights"));
+    const float* dl = static_cast<const float*>(dev_ptr(dlogits, at::kFloat, "dlogits"));
+    TORCH_CHECK_VALUE(weights.numel() >= t.nw && dlogits.numel() >= n * out_dim, "weights / dlogits are smaller than the network / [n, out_dim]");
+    TORCH_CHECK_TYPE(scratch.is_cuda() && scratch.scalar_type() == at::kByte && scratch.is_contiguous() && scratch.numel() >= t.bytes,
+                     "scratch: expected the ", t.bytes, "-byte device buffer of inr_forward_f32");
+    std::optional<at::Device> dev = weights.device();
+    same_device(dev, dlogits, "dlogits");
+    same_device(dev, scratch, "scratch");
+    DeviceGuard guard(*dev);
+    const auto f32 = at::TensorOptions().dtype(at::kFloat).device(*dev);
+    Tensor gw = at::empty({ t.nw }, f32), gb = at::empty({ t.nb }, f32);
+    check(mrirt_inr_backward(&t.d, w, n, dl, gw.data_ptr<float>(), gb.data_ptr<float>(), 0u, scratch.data_ptr(), scratch.numel(),
+                             current_stream()), "mrirt_inr_backward");
+    return { gw, gb };
+}
+
 // the volume's extent and spacing as the C ABI takes them; every label tensor is int16 (H, W, D) on one device
 void edt_args(const Tensor& first, const OptTensor& second, at::ArrayRef<double> spacing, uint32_t hwd[3], float sp[3],
               std::optional<at::Device>& dev) {
@@ -353,6 +435,11 @@ TORCH_LIBRARY(mrirt_native, m) {
     m.def("render_mesh(Tensor params, Tensor ext, Tensor nodes, Tensor tris, Tensor verts, int max_depth) -> Tensor");
     m.def("inr_forward(Tensor weights, Tensor biases, int kind, int num_layers, int in_dim, int out_dim, int hidden, "
           "int fourier_freqs, int num_mods, float w0, Tensor? coords, Tensor? feats, int n) -> Tensor");
+    m.def("inr_forward_f32(Tensor weights, Tensor biases, int kind, int num_layers, int in_dim, int out_dim, int hidden, "
+          "int fourier_freqs, int num_mods, Tensor? coords, Tensor? feats, int n) -> (Tensor, Tensor)");
+    m.def("inr_loss(Tensor logits, Tensor labels, float[] class_weights, float dice_weight) -> (Tensor, Tensor, Tensor)");
+    m.def("inr_backward(Tensor weights, Tensor dlogits, Tensor scratch, int kind, int num_layers, int in_dim, int out_dim, int hidden, "
+          "int fourier_freqs, int num_mods, int n) -> (Tensor, Tensor)");
     m.def("edt_squared(Tensor labels, int cls, float[] spacing) -> Tensor");
     m.def("hausdorff(Tensor pred, Tensor truth, float[] spacing, int num_classes) -> Tensor");
     m.def("surface_count(Tensor labels, int class_mask) -> Tensor");
@@ -368,6 +455,9 @@ TORCH_LIBRARY_IMPL(mrirt_native, CompositeExplicitAutograd, m) {
     m.impl("render_sdf", &render_sdf);
     m.impl("render_mesh", &render_mesh);
     m.impl("inr_forward", &inr_forward);
+    m.impl("inr_forward_f32", &inr_forward_f32);
+    m.impl("inr_loss", &inr_loss);
+    m.impl("inr_backward", &inr_backward);
     m.impl("edt_squared", &edt_squared);
     m.impl("hausdorff", &hausdorff);
     m.impl("surface_count", &surface_count);

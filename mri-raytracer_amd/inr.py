@@ -450,3 +450,148 @@ def render_brats_inr(params, intensities, net: PackedMLP, zmu, zsigma, labels=No
 def labels_for_viewer(pred_hwd: torch.Tensor) -> torch.Tensor:
     """pred (H,W,D) -> the viewer's x-fastest uint32 label buffer (brats_viewer.py:297-299)."""
     return pred_hwd.permute(2, 1, 0).reshape(-1).to(torch.int32).contiguous()
+
+
+# --- training step: fp32 forward, loss and weight gradients (csrc/inr_train.hip) ------------------------------------------------
+def train_desc(dims: Sequence[int], fourier_freqs: Optional[int] = None, num_mods: int = 0) -> _lib.InrDesc:
+    """Descriptor of a ReLU network ``dims = [in, hidden, .., hidden, out]`` for the fp32 training entry points:
+    ``fourier_freqs=None`` is the raw kind (the input matrix is given), otherwise the Fourier kind over ``num_mods``
+    intensities.  The packed inference images (``desc.weights`` / ``desc.biases``) stay unset: nothing here reads them."""
+    dims = [int(v) for v in dims]
+    if len(dims) < 3 or any(v != dims[1] for v in dims[1:-1]):
+        raise ValueError(f"layer widths {dims}: the kernels need at least one hidden layer and equal hidden widths")
+    d = _lib.InrDesc()
+    d.kind = KIND_RAW_RELU if fourier_freqs is None else KIND_FOURIER_RELU
+    d.numLayers, d.inDim, d.hidden, d.outDim = len(dims) - 1, dims[0], dims[1], dims[-1]
+    d.fourierFreqs, d.numMods = (0, 0) if fourier_freqs is None else (int(fourier_freqs), int(num_mods))
+    return d
+
+
+def _param_dims(Ws, bs) -> List[int]:
+    dims = [int(Ws[0].shape[0])] + [int(W.shape[1]) for W in Ws]
+    for i, (W, b) in enumerate(zip(Ws, bs)):
+        if tuple(W.shape) != (dims[i], dims[i + 1]) or tuple(b.shape) != (dims[i + 1],):
+            raise ValueError(f"layer {i}: W {tuple(W.shape)} / b {tuple(b.shape)} do not chain")
+    return dims
+
+
+def train_scratch(desc: _lib.InrDesc, n: int, dev) -> torch.Tensor:
+    nbytes = int(_lib.lib().mrirt_inr_train_scratch_bytes(C.byref(desc), int(n)))
+    if nbytes <= 0:
+        raise ValueError(f"unsupported training shape: in {desc.inDim}, hidden {desc.hidden} x {desc.numLayers - 1}, out {desc.outDim}, "
+                         f"n {n} (ReLU kinds, hidden in {{32,64,128,256}}, in <= 128, out <= 16, <= 8 layers, n >= 1)")
+    return torch.empty(nbytes, dtype=torch.uint8, device=dev)
+
+
+def forward_f32(desc: _lib.InrDesc, w_flat: torch.Tensor, b_flat: torch.Tensor, coords, feats, n: int, scratch: torch.Tensor):
+    """``mrirt_inr_forward_f32``: fp32 logits (n, out); the activations the backward pass needs stay in ``scratch``."""
+    logits = torch.empty((int(n), int(desc.outDim)), dtype=torch.float32, device=w_flat.device)
+    rc = _lib.lib().mrirt_inr_forward_f32(C.byref(desc), _ptr(w_flat), _ptr(b_flat), _ptr(coords), _ptr(feats), int(n), _ptr(logits),
+                                          _ptr(scratch), scratch.numel(), _stream_ptr(None))
+    _lib.check(rc, "mrirt_inr_forward_f32")
+    return logits
+
+
+def loss_and_dlogits(logits: torch.Tensor, labels: torch.Tensor, class_weights, dice_weight: float, scratch=None,
+                     want_grad: bool = True):
+    """``mrirt_inr_loss`` on (n, C) logits and int32 labels: (loss 0-d, aux (2, C): CE per class, Dice per class,
+    dlogits (n, C) or None), all on the device."""
+    n, nc = int(logits.shape[0]), int(logits.shape[1])
+    cw = [float(np.float32(v)) for v in class_weights]
+    if len(cw) != nc:
+        raise ValueError(f"class_weights holds {len(cw)} values for {nc} classes")
+    dev = logits.device
+    if scratch is None:
+        scratch = torch.empty(max(int(_lib.lib().mrirt_inr_loss_scratch_bytes(n)), 16), dtype=torch.uint8, device=dev)
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    aux = torch.empty((2, nc), dtype=torch.float32, device=dev)
+    dl = torch.empty_like(logits) if want_grad else None
+    rc = _lib.lib().mrirt_inr_loss(_ptr(logits), _ptr(labels), n, nc, (C.c_float * nc)(*cw), float(dice_weight), _ptr(loss), _ptr(aux),
+                                   _ptr(dl), _ptr(scratch), scratch.numel(), _stream_ptr(None))
+    _lib.check(rc, "mrirt_inr_loss")
+    return loss.reshape(()), aux, dl
+
+
+def backward_f32(desc: _lib.InrDesc, w_flat: torch.Tensor, n: int, dlogits: torch.Tensor, scratch: torch.Tensor,
+                 grad_w: Optional[torch.Tensor] = None, grad_b: Optional[torch.Tensor] = None, accumulate: bool = False):
+    """``mrirt_inr_backward``: (grad_w, grad_b) in the flat layouts of the weights / biases, from what ``forward_f32`` left in
+    ``scratch``.  ``accumulate`` adds into the given buffers."""
+    nb = int(desc.hidden) * (int(desc.numLayers) - 1) + int(desc.outDim)
+    gw = grad_w if grad_w is not None else torch.empty_like(w_flat)
+    gb = grad_b if grad_b is not None else torch.empty(nb, dtype=torch.float32, device=w_flat.device)
+    rc = _lib.lib().mrirt_inr_backward(C.byref(desc), _ptr(w_flat), int(n), _ptr(dlogits), _ptr(gw), _ptr(gb), 1 if accumulate else 0,
+                                       _ptr(scratch), scratch.numel(), _stream_ptr(None))
+    _lib.check(rc, "mrirt_inr_backward")
+    return gw, gb
+
+
+def _split_grads(gw: torch.Tensor, gb: torch.Tensor, dims: Sequence[int]):
+    out, wo, bo = [], 0, 0
+    for i in range(len(dims) - 1):
+        a, b = dims[i], dims[i + 1]
+        out.append({"W": gw[wo:wo + a * b].view(a, b), "b": gb[bo:bo + b]})
+        wo, bo = wo + a * b, bo + b
+    return out
+
+
+def make_loss_and_grad(num_classes: int, class_weights, dice_weight: float, fourier_freqs: int):
+    """inr/inr/model.py:64-90 on the GPU: returns ``f(params, coords, intensities, labels) -> ((loss, aux), grads)`` with the
+    reference's return shape — ``loss`` a 0-d device tensor, ``aux = {"ce_per_class", "dice_per_class"}`` (device, (C,)),
+    ``grads`` a list of ``{"W", "b"}`` device tensors shaped like ``params`` (NumPy arrays or device tensors).  One fp32
+    forward, the loss and one backward pass (csrc/inr_train.hip); nothing synchronises with the host."""
+    cw = [float(v) for v in np.asarray(class_weights, dtype=np.float32).reshape(-1)]
+    if len(cw) != int(num_classes):
+        raise ValueError(f"class_weights holds {len(cw)} values for {num_classes} classes")
+
+    def loss_and_grad(params, coords, intensities, labels):
+        dev = _require_gpu()
+        Ws = [_dev_f32(p["W"], dev) for p in params]
+        bs = [_dev_f32(p["b"], dev) for p in params]
+        dims = _param_dims(Ws, bs)
+        if dims[-1] != int(num_classes):
+            raise ValueError(f"the network has {dims[-1]} outputs for {num_classes} classes")
+        c, f = _dev_f32(coords, dev), _dev_f32(intensities, dev)
+        n = int(c.shape[0])
+        lab = torch.as_tensor(labels).to(dev).to(torch.int32).contiguous()
+        desc = train_desc(dims, fourier_freqs, f.shape[1] if f.dim() == 2 else 0)
+        w_flat, b_flat = torch.cat([W.reshape(-1) for W in Ws]), torch.cat(bs)
+        scratch = train_scratch(desc, n, dev)
+        logits = forward_f32(desc, w_flat, b_flat, c, f, n, scratch)
+        loss, aux, dl = loss_and_dlogits(logits, lab, cw, dice_weight, scratch)
+        gw, gb = backward_f32(desc, w_flat, n, dl, scratch)
+        return (loss, {"ce_per_class": aux[0], "dice_per_class": aux[1]}), _split_grads(gw, gb, dims)
+
+    return loss_and_grad
+
+
+class _MlpF32(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, coords, feats, fourier_freqs, num_layers, *wb):
+        Ws, bs = wb[:num_layers], wb[num_layers:]
+        dims = _param_dims(Ws, bs)
+        dev = Ws[0].device
+        n = int(feats.shape[0]) if fourier_freqs is None else int(coords.shape[0])
+        desc = train_desc(dims, fourier_freqs, 0 if fourier_freqs is None else (feats.shape[1] if feats is not None else 0))
+        w_flat = torch.cat([W.detach().to(torch.float32).reshape(-1) for W in Ws])
+        b_flat = torch.cat([b.detach().to(torch.float32).reshape(-1) for b in bs])
+        scratch = train_scratch(desc, n, dev)
+        logits = forward_f32(desc, w_flat, b_flat, coords, feats, n, scratch)
+        ctx.desc, ctx.dims, ctx.n, ctx.w_flat, ctx.scratch = desc, dims, n, w_flat, scratch
+        return logits
+
+    @staticmethod
+    def backward(ctx, grad_logits):
+        gw, gb = backward_f32(ctx.desc, ctx.w_flat, ctx.n, grad_logits.to(torch.float32).contiguous(), ctx.scratch)
+        g = _split_grads(gw, gb, ctx.dims)
+        return (None, None, None, None, *[x["W"] for x in g], *[x["b"] for x in g])
+
+
+def mlp_autograd(Ws, bs, coords, feats, fourier_freqs: Optional[int] = None) -> torch.Tensor:
+    """Differentiable fp32 logits (n, out) of a ReLU MLP: the forward is ``mrirt_inr_forward_f32``, the backward
+    ``mrirt_inr_backward`` — gradients reach ``Ws`` (each (in, out)) and ``bs`` only, so any torch loss and optimiser can fit
+    the network.  ``fourier_freqs=None``: ``feats`` is the (n, in) input matrix and ``coords`` is unused; otherwise the
+    inputs are built from coords (n, 3) and intensities ``feats`` (n, M) as ``build_input`` does."""
+    dev = Ws[0].device
+    c = _dev_f32(coords, dev) if coords is not None else None
+    f = _dev_f32(feats, dev) if feats is not None else None
+    return _MlpF32.apply(c, f, fourier_freqs, len(Ws), *Ws, *bs)

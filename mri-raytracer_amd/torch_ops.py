@@ -456,3 +456,112 @@ def surface_extract(labels: torch.Tensor, class_mask: int, spacing: Sequence[flo
 def _(labels, class_mask, spacing, origin, num_verts, num_tris):
     return (torch.empty((num_verts, 3), dtype=torch.float32, device=labels.device),
             torch.empty((num_tris, 3), dtype=torch.int32, device=labels.device))
+
+
+# --- INR training step (fp32; csrc/inr_train.hip) -----------------------------------------------
+def _train_desc(kind: int, num_layers: int, in_dim: int, out_dim: int, hidden: int, fourier_freqs: int, num_mods: int, n: int):
+    d = _lib.InrDesc()
+    d.kind, d.numLayers, d.inDim, d.outDim, d.hidden = kind, num_layers, in_dim, out_dim, hidden
+    d.fourierFreqs, d.numMods = fourier_freqs, num_mods
+    nbytes = int(_lib.lib().mrirt_inr_train_scratch_bytes(C.byref(d), int(n)))
+    if nbytes <= 0:
+        raise ValueError("unsupported network kind / shape / n for the training step (ReLU kinds only)")
+    nw = in_dim * hidden + (num_layers - 2) * hidden * hidden + hidden * out_dim
+    nb = (num_layers - 1) * hidden + out_dim
+    return d, nbytes, nw, nb
+
+
+@torch.library.custom_op("mrirt::inr_forward_f32", mutates_args=())
+def inr_forward_f32(weights: torch.Tensor, biases: torch.Tensor, kind: int, num_layers: int, in_dim: int, out_dim: int,
+                    hidden: int, fourier_freqs: int, num_mods: int, coords: Optional[torch.Tensor], feats: Optional[torch.Tensor],
+                    n: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(logits fp32 [n, out_dim], scratch uint8) of mrirt_inr_forward_f32: ``weights`` fp32 row-major [in, out] per layer,
+    concatenated unpadded, ``biases`` concatenated unpadded; kind 0 (coords [n, 3] + feats [n, num_mods]) or 2 (feats is the
+    [n, in_dim] input matrix).  ``scratch`` holds the activations ``inr_backward`` reads."""
+    d, nbytes, nw, nb = _train_desc(kind, num_layers, in_dim, out_dim, hidden, fourier_freqs, num_mods, n)
+    w = _dev_flat(weights, torch.float32, "weights")
+    b = _dev_flat(biases, torch.float32, "biases")
+    if w.numel() < nw or b.numel() < nb:
+        raise ValueError(f"weights / biases hold {w.numel()} / {b.numel()} floats, the network has {nw} / {nb}")
+    co = _dev_flat(coords, torch.float32, "coords")
+    fe = _dev_flat(feats, torch.float32, "feats")
+    if kind < 2 and (co is None or co.numel() < 3 * n):
+        raise ValueError("coords must hold [n, 3] floats")
+    width = in_dim if kind >= 2 else num_mods
+    if width > 0 and (fe is None or fe.numel() < width * n):
+        raise ValueError(f"feats must hold [n, {width}] floats")
+    dev = _one_device([("weights", w), ("biases", b), ("coords", co), ("feats", fe)])
+    with torch.cuda.device(dev):
+        out = torch.empty((n, out_dim), dtype=torch.float32, device=dev)
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        rc = _lib.lib().mrirt_inr_forward_f32(C.byref(d), _ptr(w), _ptr(b), _ptr(co), _ptr(fe), int(n), _ptr(out), _ptr(scratch),
+                                              nbytes, _stream())
+    _lib.check(rc, "mrirt_inr_forward_f32")
+    return out, scratch
+
+
+@inr_forward_f32.register_fake
+def _(weights, biases, kind, num_layers, in_dim, out_dim, hidden, fourier_freqs, num_mods, coords, feats, n):
+    return (torch.empty((n, out_dim), dtype=torch.float32, device=weights.device),
+            torch.empty(_train_desc(kind, num_layers, in_dim, out_dim, hidden, fourier_freqs, num_mods, n)[1], dtype=torch.uint8,
+                        device=weights.device))
+
+
+@torch.library.custom_op("mrirt::inr_loss", mutates_args=())
+def inr_loss(logits: torch.Tensor, labels: torch.Tensor, class_weights: Sequence[float],
+             dice_weight: float) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(loss fp32 [1], aux fp32 [2, C]: CE per class and Dice per class, dlogits fp32 [n, C]) of mrirt_inr_loss
+    (inr/inr/model.py:64-88) on logits [n, C] and int32 labels [n]."""
+    z = _dev_flat(logits, torch.float32, "logits")
+    lab = _dev_flat(labels, torch.int32, "labels")
+    if z.dim() != 2 or z.shape[0] < 1 or lab.numel() != z.shape[0]:
+        raise ValueError("logits must be [n, C] with n >= 1 and labels [n]")
+    n, nc = int(z.shape[0]), int(z.shape[1])
+    if not 1 <= nc <= 16 or len(class_weights) != nc:
+        raise ValueError("1..16 classes, one class weight each")
+    dev = _one_device([("logits", z), ("labels", lab)])
+    lib = _lib.lib()
+    with torch.cuda.device(dev):
+        nbytes = int(lib.mrirt_inr_loss_scratch_bytes(n))
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        aux = torch.empty((2, nc), dtype=torch.float32, device=dev)
+        dl = torch.empty_like(z)
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        rc = lib.mrirt_inr_loss(_ptr(z), _ptr(lab), n, nc, (C.c_float * nc)(*[float(np.float32(v)) for v in class_weights]),
+                                float(dice_weight), _ptr(loss), _ptr(aux), _ptr(dl), _ptr(scratch), nbytes, _stream())
+    _lib.check(rc, "mrirt_inr_loss")
+    return loss, aux, dl
+
+
+@inr_loss.register_fake
+def _(logits, labels, class_weights, dice_weight):
+    return (torch.empty(1, dtype=torch.float32, device=logits.device),
+            torch.empty((2, logits.shape[1]), dtype=torch.float32, device=logits.device), torch.empty_like(logits))
+
+
+@torch.library.custom_op("mrirt::inr_backward", mutates_args=())
+def inr_backward(weights: torch.Tensor, dlogits: torch.Tensor, scratch: torch.Tensor, kind: int, num_layers: int, in_dim: int,
+                 out_dim: int, hidden: int, fourier_freqs: int, num_mods: int, n: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(grad_w, grad_b) in the flat layouts of the weights / biases through mrirt_inr_backward, from dlogits [n, out_dim] and
+    the ``scratch`` that ``inr_forward_f32`` returned for the same network and n."""
+    d, nbytes, nw, nb = _train_desc(kind, num_layers, in_dim, out_dim, hidden, fourier_freqs, num_mods, n)
+    w = _dev_flat(weights, torch.float32, "weights")
+    dl = _dev_flat(dlogits, torch.float32, "dlogits")
+    if w.numel() < nw or dl.numel() < n * out_dim:
+        raise ValueError("weights / dlogits are smaller than the network / [n, out_dim]")
+    if not scratch.is_cuda or scratch.dtype != torch.uint8 or scratch.numel() < nbytes:
+        raise TypeError(f"scratch: expected the {nbytes}-byte device buffer of inr_forward_f32")
+    dev = _one_device([("weights", w), ("dlogits", dl), ("scratch", scratch)])
+    with torch.cuda.device(dev):
+        gw = torch.empty(nw, dtype=torch.float32, device=dev)
+        gb = torch.empty(nb, dtype=torch.float32, device=dev)
+        rc = _lib.lib().mrirt_inr_backward(C.byref(d), _ptr(w), int(n), _ptr(dl), _ptr(gw), _ptr(gb), 0, _ptr(scratch),
+                                           scratch.numel(), _stream())
+    _lib.check(rc, "mrirt_inr_backward")
+    return gw, gb
+
+
+@inr_backward.register_fake
+def _(weights, dlogits, scratch, kind, num_layers, in_dim, out_dim, hidden, fourier_freqs, num_mods, n):
+    _, _, nw, nb = _train_desc(kind, num_layers, in_dim, out_dim, hidden, fourier_freqs, num_mods, n)
+    return (torch.empty(nw, dtype=torch.float32, device=weights.device), torch.empty(nb, dtype=torch.float32, device=weights.device))
