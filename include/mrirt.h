@@ -31,7 +31,10 @@ extern "C" {
 /*    Backward-compatible additions under the same version: MrirtMeshParams + mrirt_render_mesh (K4, the triangle-mesh BVH
  *    ray tracer), mrirt_sizeof(6); mrirt_edt_scratch_bytes, mrirt_edt_squared, mrirt_hausdorff (no new struct);
  *    mrirt_surface_scratch_bytes, mrirt_surface_count, mrirt_surface_extract (no new struct);
- *    mrirt_render_brats_backward (the K1 backward pass on LINEAR grids; no new struct). */
+ *    mrirt_render_brats_backward (the K1 backward pass on LINEAR grids; no new struct);
+ *    the INR training loop: MrirtInrCache, MrirtAdamW, MrirtInrTrainCfg, MrirtInrTrainState (mrirt_sizeof(7..10)),
+ *    mrirt_inr_sample_batch, mrirt_inr_adamw_scratch_bytes, mrirt_inr_adamw_step, mrirt_inr_lr_schedule,
+ *    mrirt_inr_train_run_scratch_bytes, mrirt_inr_train_run. */
 #define MRIRT_ABI_VERSION 4
 
 typedef enum MrirtStatus {
@@ -385,7 +388,8 @@ typedef enum MrirtInrFlags {
 
 /* bytes to allocate for the packed weight buffer of a network shape (0: unsupported shape): the bf16 MFMA image,
  * 64 KiB of slack (the kernel's last weight-chunk prefetch reads and ignores it), the split-bf16 (hi + lo) image the
- * near-tie refinement reads, and a 1 KiB calibration record. */
+ * near-tie refinement reads, 32 KiB of slack after it (the refinement's tile DMA always moves a full ring slot), and a
+ * 1 KiB calibration record.  Size the buffer from this function, never from this list. */
 int64_t mrirt_inr_pack_bytes(const MrirtInrDesc* desc);
 /* pack fp32 row-major [in,out] weights (device, layers concatenated unpadded) into `packed`.  The images depend on
  * desc->kind and desc->w0 (the SIREN's w0 / 2 pi and 1 / 2 pi are folded in): pack and forward with the same
@@ -439,6 +443,81 @@ int mrirt_inr_loss(const float* logits, const int32_t* labels, int64_t n, uint32
  * the same desc and n: dW_l = h_{l-1}^T dz_l, db_l = sum_p dz_l, dz_{l-1} = (dz_l W_l^T) where z_{l-1} > 0, else 0. */
 int mrirt_inr_backward(const MrirtInrDesc* desc, const float* w_f32, int64_t n, const float* dlogits, float* grad_w,
                        float* grad_b, uint32_t flags, void* scratch, int64_t scratch_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------ */
+/* INR training loop (inr/inr/train.py:18-259, inr/inr/dataloader.py:86-96,133-155)      */
+/* ------------------------------------------------------------------------------------ */
+/* A device-resident set of cases of one shape: case k is mods[k] = float [numMods][H][W][D] and seg[k] = int16 [H][W][D],
+ * C order (what mrirt_inr_predict_volume reads).  `mods` and `seg` are DEVICE arrays of ncases device pointers (mods may be
+ * NULL when numMods == 0).  Every axis >= 2, H W D < 2^31, numMods <= 8, 1 <= ncases <= 65535. */
+typedef struct MrirtInrCache {
+    const float* const* mods;
+    const int16_t* const* seg;
+    uint32_t ncases, numMods;
+    uint32_t hwd[3];
+    uint32_t reserved;
+} MrirtInrCache;
+
+/* Micro-batch `batch_index` of the stream `seed`: n voxels drawn with Philox4x32-10, point i from key (seed lo, seed hi) and
+ * counter (i, batch_index lo, batch_index hi, 0); its output words r0..r3 give case = mulhi32(r0, ncases), x = mulhi32(r1, H),
+ * y = mulhi32(r2, W), z = mulhi32(r3, D) with mulhi32(r, m) = (r m) >> 32 (no rejection step: a value's probability is off
+ * by at most m / 2^32).  coords[n][3] = (float(x) / float(H - 1)) * 2 - 1 ..., feats[n][numMods] = mods[case][m][x][y][z],
+ * labels[n] = seg[case][x][y][z] widened to int32 — the three arrays mrirt_inr_forward_f32 / mrirt_inr_loss take.  The same
+ * arguments give the same bits.  1 <= n < 2^31; feats may be NULL when numMods == 0.  No host synchronisation. */
+int mrirt_inr_sample_batch(const MrirtInrCache* cache, uint64_t seed, uint64_t batch_index, int64_t n, float* coords,
+                           float* feats, int32_t* labels, void* stream);
+
+/* optax.chain(clip_by_global_norm(clipNorm), adamw(lr)) for one update.  lr is the step's (already scheduled) rate. */
+typedef struct MrirtAdamW {
+    float lr, b1, b2, eps, weightDecay;
+    float clipNorm;          /* <= 0 or +inf: no clipping */
+} MrirtAdamW;
+
+/* Update number t + 1 (t = updates already applied) of the nw weights and nb biases in place, with their first and second
+ * moments, from the gradients gw / gb scaled by gscale:
+ *   g = grad gscale;  norm = sqrt(sum g^2) over gw then gb, in fp64 (fixed order, no atomics);
+ *   s = float(norm < clipNorm ? 1 : clipNorm / norm), NaN for a non-finite norm; 1 without clipping;
+ *   gc = g s;  mu = b1 mu + (1 - b1) gc;  nu = b2 nu + ((1 - b2) gc) gc;  mh = mu / (1 - b1^(t+1));  nh = nu / (1 - b2^(t+1));
+ *   p = p - lr (mh / (sqrtf(nh) + eps) + weightDecay p)
+ * in fp32 without contraction; 1 - b1, 1 - b2, 1 - b1^(t+1), 1 - b2^(t+1) are evaluated in fp64 and rounded to fp32.
+ * gnorm: two doubles on the device, [0] = norm, [1] = s (widened).  nw >= 1, nb >= 0, nw + nb < 2^31; hyper-parameters
+ * finite (clipNorm may be +inf), 0 <= b1, b2 < 1, eps > 0, gscale finite.  scratch: device, 16-byte aligned,
+ * mrirt_inr_adamw_scratch_bytes(nw + nb) bytes.  No host synchronisation: s is read on the device. */
+int64_t mrirt_inr_adamw_scratch_bytes(int64_t n);
+int mrirt_inr_adamw_step(float* w, float* b, const float* gw, const float* gb, float* mu_w, float* mu_b, float* nu_w,
+                         float* nu_b, int64_t nw, int64_t nb, const MrirtAdamW* hp, uint64_t t, float gscale, double* gnorm,
+                         void* scratch, int64_t scratch_bytes, void* stream);
+
+/* optax.warmup_cosine_decay_schedule(0, peak, warmup, decay_steps, end) at t updates already applied, in fp64:
+ * t < warmup: peak t / warmup; else T = decay_steps - warmup (T <= 0: MRIRT_ERR_ARG, as optax asserts), u = min(t - warmup, T) / T,
+ * lr = peak ((1 - a) 0.5 (1 + cos(pi u)) + a), a = end / peak.  peak > 0, end >= 0, both finite.  Host only. */
+int mrirt_inr_lr_schedule(double peak, double end, uint32_t warmup, uint32_t decay_steps, uint64_t t, double* lr);
+
+typedef struct MrirtInrTrainCfg {
+    int64_t microBatch;          /* points per micro-batch, 1 .. 2^31 - 1                            */
+    uint32_t accum;              /* micro-batches per update, >= 1; gradients are scaled by 1 / accum */
+    uint32_t warmupSteps, decaySteps, reserved;      /* the schedule's warmup and decay_steps         */
+    uint64_t seed;
+    double peakLr, minLr;
+    float classWeights[16];      /* the first desc->outDim are read                                   */
+    float diceWeight;
+    MrirtAdamW adamw;            /* lr is not read: the schedule sets it                              */
+} MrirtInrTrainCfg;
+
+typedef struct MrirtInrTrainState {      /* device pointers, the flat layouts of mrirt_inr_forward_f32 */
+    float *w, *b, *mu_w, *mu_b, *nu_w, *nu_b;
+} MrirtInrTrainState;
+
+/* Enqueues `steps` optimiser steps: step k runs accum x (mrirt_inr_sample_batch with batch_index (first_step + k) accum + a
+ * -> mrirt_inr_forward_f32 -> mrirt_inr_loss -> mrirt_inr_backward, flags 0 for a = 0 and bit 0 after) and one
+ * mrirt_inr_adamw_step with gscale = 1 / accum, t = first_step + k and lr = the schedule at t: the bits of the separate calls.
+ * desc: MRIRT_INR_FOURIER_RELU with numMods == cache->numMods; outDim is the number of classes.  history (device):
+ * [steps][accum][1 + 2 outDim] floats, per micro-batch the loss, then CE per class, then Dice per class.  Every argument is
+ * checked before anything is launched; no host synchronisation, no allocation.  scratch: device, 16-byte aligned. */
+int64_t mrirt_inr_train_run_scratch_bytes(const MrirtInrDesc* desc, const MrirtInrCache* cache, const MrirtInrTrainCfg* cfg);
+int mrirt_inr_train_run(const MrirtInrDesc* desc, const MrirtInrCache* cache, const MrirtInrTrainCfg* cfg,
+                        const MrirtInrTrainState* state, uint64_t first_step, uint32_t steps, float* history, void* scratch,
+                        int64_t scratch_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------ */
 /* Exact distance transform and Hausdorff distance (inr/inr/model.py:164-195)            */
@@ -549,7 +628,7 @@ int mrirt_abi_version(void);
 const char* mrirt_status_string(int status);
 int mrirt_last_hip_error(void);            /* hipError_t of the last failed HIP call on this thread */
 uint32_t mrirt_sizeof(uint32_t which);     /* 0 BratsParams, 1 RenderExt, 2 VolumeParams, 3 SdfParams, 4 InrDesc, 5 Skip,
-                                              6 MeshParams */
+                                              6 MeshParams, 7 InrCache, 8 AdamW, 9 InrTrainCfg, 10 InrTrainState */
 /* Opt-in diagnostics (host only; the library installs nothing by itself): a SIGABRT handler that writes the native
  * backtrace of the aborting thread and, when file descriptor 2 has been redirected into a regular file (a test runner's
  * capture), the tail of that file to `fd` — a descriptor the caller duplicated before the redirection — and then chains

@@ -17,7 +17,7 @@ CSRC = PKG_DIR / "csrc"
 INCLUDE = PKG_DIR.parent / "include"
 SO_PATH = pathlib.Path(os.environ.get("MRIRT_LIB", PKG_DIR / "libmrirt.so"))   # override: A/B builds in development
 HIP_SOURCES = ["brats_march.hip", "brats_skip.hip", "brats_c5.hip", "brats_slab.hip", "brats_ring.hip", "brats_backward.hip", "volume_march.hip", "grid_ops.hip", "inr_mlp.hip",
-               "inr_train.hip", "mesh_rt.hip", "edt.hip", "surface.hip", "abort_trace.cpp"]
+               "inr_train.hip", "inr_optim.hip", "mesh_rt.hip", "edt.hip", "surface.hip", "abort_trace.cpp"]
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17", "-Wall"]
 
 # every extern "C" symbol include/mrirt.h declares
@@ -33,6 +33,8 @@ ABI_SYMBOLS = [
     "mrirt_surface_scratch_bytes", "mrirt_surface_count", "mrirt_surface_extract",
     "mrirt_render_brats_backward",
     "mrirt_inr_train_scratch_bytes", "mrirt_inr_loss_scratch_bytes", "mrirt_inr_forward_f32", "mrirt_inr_loss", "mrirt_inr_backward",
+    "mrirt_inr_sample_batch", "mrirt_inr_adamw_scratch_bytes", "mrirt_inr_adamw_step", "mrirt_inr_lr_schedule",
+    "mrirt_inr_train_run_scratch_bytes", "mrirt_inr_train_run",
 ]
 
 ABI_VERSION = 4          # MRIRT_ABI_VERSION of include/mrirt.h this binding was written against
@@ -112,6 +114,25 @@ class InrDesc(C.Structure):
         ("weights", C.c_void_p), ("biases", C.c_void_p),
         ("flags", u32), ("tieSigmas", f32),
     ]
+
+
+class InrCache(C.Structure):
+    """MrirtInrCache: device tables of per-case mods / seg pointers."""
+    _fields_ = [("mods", C.c_void_p), ("seg", C.c_void_p), ("ncases", u32), ("numMods", u32), ("hwd", u32 * 3), ("reserved", u32)]
+
+
+class AdamW(C.Structure):
+    _fields_ = [("lr", f32), ("b1", f32), ("b2", f32), ("eps", f32), ("weightDecay", f32), ("clipNorm", f32)]
+
+
+class InrTrainCfg(C.Structure):
+    _fields_ = [("microBatch", C.c_int64), ("accum", u32), ("warmupSteps", u32), ("decaySteps", u32), ("reserved", u32),
+                ("seed", C.c_uint64), ("peakLr", C.c_double), ("minLr", C.c_double), ("classWeights", f32 * 16), ("diceWeight", f32),
+                ("adamw", AdamW)]
+
+
+class InrTrainState(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("w", "b", "mu_w", "mu_b", "nu_w", "nu_b")]
 
 
 class Skip(C.Structure):
@@ -334,6 +355,20 @@ def lib() -> C.CDLL:
     l.mrirt_inr_loss.restype = i32
     l.mrirt_inr_backward.argtypes = [C.POINTER(InrDesc), vp, i64, vp, vp, vp, u32, vp, i64, vp]
     l.mrirt_inr_backward.restype = i32
+    u64 = C.c_uint64
+    l.mrirt_inr_sample_batch.argtypes = [C.POINTER(InrCache), u64, u64, i64, vp, vp, vp, vp]
+    l.mrirt_inr_sample_batch.restype = i32
+    l.mrirt_inr_adamw_scratch_bytes.argtypes = [i64]
+    l.mrirt_inr_adamw_scratch_bytes.restype = i64
+    l.mrirt_inr_adamw_step.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, C.POINTER(AdamW), u64, f32, vp, vp, i64, vp]
+    l.mrirt_inr_adamw_step.restype = i32
+    l.mrirt_inr_lr_schedule.argtypes = [C.c_double, C.c_double, u32, u32, u64, C.POINTER(C.c_double)]
+    l.mrirt_inr_lr_schedule.restype = i32
+    l.mrirt_inr_train_run_scratch_bytes.argtypes = [C.POINTER(InrDesc), C.POINTER(InrCache), C.POINTER(InrTrainCfg)]
+    l.mrirt_inr_train_run_scratch_bytes.restype = i64
+    l.mrirt_inr_train_run.argtypes = [C.POINTER(InrDesc), C.POINTER(InrCache), C.POINTER(InrTrainCfg), C.POINTER(InrTrainState), u64, u32,
+                                      vp, vp, i64, vp]
+    l.mrirt_inr_train_run.restype = i32
     l.mrirt_status_string.argtypes = [i32]
     l.mrirt_status_string.restype = C.c_char_p
     l.mrirt_sizeof.argtypes = [u32]
@@ -346,7 +381,8 @@ def lib() -> C.CDLL:
     if l.mrirt_abi_version() != ABI_VERSION:
         raise ImportError(f"ABI mismatch: {SO_PATH} reports version {l.mrirt_abi_version()}, this binding expects {ABI_VERSION} "
                           "(rebuild: python -c \"import __graft_entry__ as g; g.build()\")")
-    for which, st in enumerate((BratsParams, RenderExt, VolumeParams, SdfParams, InrDesc, Skip, MeshParams)):
+    for which, st in enumerate((BratsParams, RenderExt, VolumeParams, SdfParams, InrDesc, Skip, MeshParams, InrCache, AdamW, InrTrainCfg,
+                                InrTrainState)):
         if l.mrirt_sizeof(which) != C.sizeof(st):
             raise ImportError(f"ABI mismatch: {st.__name__} is {C.sizeof(st)} B here, {l.mrirt_sizeof(which)} B in {SO_PATH}")
     _LIB = l

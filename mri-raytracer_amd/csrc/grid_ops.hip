@@ -446,6 +446,10 @@ extern "C" uint32_t mrirt_sizeof(uint32_t which) {
         case 4: return (uint32_t)sizeof(MrirtInrDesc);
         case 5: return (uint32_t)sizeof(MrirtSkip);
         case 6: return (uint32_t)sizeof(MrirtMeshParams);
+        case 7: return (uint32_t)sizeof(MrirtInrCache);
+        case 8: return (uint32_t)sizeof(MrirtAdamW);
+        case 9: return (uint32_t)sizeof(MrirtInrTrainCfg);
+        case 10: return (uint32_t)sizeof(MrirtInrTrainState);
         default: return 0;
     }
 }

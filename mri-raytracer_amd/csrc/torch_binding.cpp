@@ -14,6 +14,7 @@
 #include <cstring>
 #include <optional>
 #include <tuple>
+#include <vector>
 
 #include "mrirt.h"
 
@@ -323,6 +324,58 @@ std::tuple<Tensor, Tensor> inr_backward(const Tensor& weights, const Tensor& dlo
     return { gw, gb };
 }
 
+// ---- INR training loop: mrirt_inr_sample_batch / mrirt_inr_adamw_step ----
+// (coords [n, 3], feats [n, num_mods], labels int32 [n]); the tables are int64 device tensors of per-case device addresses
+std::tuple<Tensor, Tensor, Tensor> inr_sample_batch(const OptTensor& mods_table, const Tensor& seg_table, int64_t num_mods, int64_t h, int64_t w,
+                                                    int64_t d, int64_t seed, int64_t batch_index, int64_t n) {
+    const void* st = dev_ptr(seg_table, at::kLong, "seg_table");
+    const void* mt = dev_ptr(mods_table, at::kLong, "mods_table");
+    TORCH_CHECK_VALUE(seg_table.numel() >= 1 && (num_mods <= 0 || (mods_table.has_value() && mods_table->numel() == seg_table.numel())),
+                      "seg_table must hold one address per case, and mods_table as many when num_mods > 0");
+    TORCH_CHECK_VALUE(num_mods >= 0 && h >= 0 && w >= 0 && d >= 0 && n >= 0, "negative extent");
+    std::optional<at::Device> dev = seg_table.device();
+    same_device(dev, mods_table, "mods_table");
+    DeviceGuard guard(*dev);
+    MrirtInrCache c;
+    std::memset(&c, 0, sizeof c);
+    c.mods = num_mods > 0 ? static_cast<const float* const*>(mt) : nullptr;
+    c.seg = static_cast<const int16_t* const*>(st);
+    c.ncases = (uint32_t)seg_table.numel(); c.numMods = (uint32_t)num_mods;
+    c.hwd[0] = (uint32_t)h; c.hwd[1] = (uint32_t)w; c.hwd[2] = (uint32_t)d;
+    const auto f32 = at::TensorOptions().dtype(at::kFloat).device(*dev);
+    Tensor coords = at::empty({ n, 3 }, f32), feats = at::empty({ n, num_mods }, f32);
+    Tensor labels = at::empty({ n }, at::TensorOptions().dtype(at::kInt).device(*dev));
+    check(mrirt_inr_sample_batch(&c, (uint64_t)seed, (uint64_t)batch_index, n, coords.data_ptr<float>(),
+                                 num_mods > 0 ? feats.data_ptr<float>() : nullptr, labels.data_ptr<int32_t>(), current_stream()),
+          "mrirt_inr_sample_batch");
+    return { coords, feats, labels };
+}
+
+// [w, b, mu_w, mu_b, nu_w, nu_b, gnorm] after update t + 1 on copies of the flat parameters and moments
+std::vector<Tensor> inr_adamw_step(const Tensor& w, const Tensor& b, const Tensor& gw, const Tensor& gb, const Tensor& mu_w, const Tensor& mu_b,
+                                   const Tensor& nu_w, const Tensor& nu_b, double lr, double b1, double b2, double eps, double weight_decay,
+                                   double clip_norm, int64_t t, double gscale) {
+    const Tensor* ten[8] = { &w, &b, &gw, &gb, &mu_w, &mu_b, &nu_w, &nu_b };
+    static const char* names[8] = { "w", "b", "gw", "gb", "mu_w", "mu_b", "nu_w", "nu_b" };
+    std::optional<at::Device> dev = w.device();
+    for (int i = 0; i < 8; ++i) {
+        dev_ptr(*ten[i], at::kFloat, names[i]);
+        same_device(dev, *ten[i], names[i]);
+        TORCH_CHECK_VALUE(ten[i]->numel() == ten[i & 1]->numel(), "gradients and moments must have the sizes of w and b");
+    }
+    DeviceGuard guard(*dev);
+    const int64_t nw = w.numel(), nb = b.numel();
+    Tensor ow = w.clone(), ob = b.clone(), omw = mu_w.clone(), omb = mu_b.clone(), onw = nu_w.clone(), onb = nu_b.clone();
+    const int64_t nbytes = mrirt_inr_adamw_scratch_bytes(nw + nb);
+    Tensor scratch = at::empty({ nbytes > 16 ? nbytes : 16 }, at::TensorOptions().dtype(at::kByte).device(*dev));
+    Tensor gnorm = at::empty({ 2 }, at::TensorOptions().dtype(at::kDouble).device(*dev));
+    const MrirtAdamW hp = { (float)lr, (float)b1, (float)b2, (float)eps, (float)weight_decay, (float)clip_norm };
+    check(mrirt_inr_adamw_step(ow.data_ptr<float>(), ob.data_ptr<float>(), gw.data_ptr<float>(), gb.data_ptr<float>(), omw.data_ptr<float>(),
+                               omb.data_ptr<float>(), onw.data_ptr<float>(), onb.data_ptr<float>(), nw, nb, &hp, (uint64_t)t, (float)gscale,
+                               gnorm.data_ptr<double>(), scratch.data_ptr(), nbytes, current_stream()), "mrirt_inr_adamw_step");
+    return { ow, ob, omw, omb, onw, onb, gnorm };
+}
+
 // the volume's extent and spacing as the C ABI takes them; every label tensor is int16 (H, W, D) on one device
 void edt_args(const Tensor& first, const OptTensor& second, at::ArrayRef<double> spacing, uint32_t hwd[3], float sp[3],
               std::optional<at::Device>& dev) {
@@ -440,6 +493,10 @@ TORCH_LIBRARY(mrirt_native, m) {
     m.def("inr_loss(Tensor logits, Tensor labels, float[] class_weights, float dice_weight) -> (Tensor, Tensor, Tensor)");
     m.def("inr_backward(Tensor weights, Tensor dlogits, Tensor scratch, int kind, int num_layers, int in_dim, int out_dim, int hidden, "
           "int fourier_freqs, int num_mods, int n) -> (Tensor, Tensor)");
+    m.def("inr_sample_batch(Tensor? mods_table, Tensor seg_table, int num_mods, int h, int w, int d, int seed, int batch_index, int n) "
+          "-> (Tensor, Tensor, Tensor)");
+    m.def("inr_adamw_step(Tensor w, Tensor b, Tensor gw, Tensor gb, Tensor mu_w, Tensor mu_b, Tensor nu_w, Tensor nu_b, float lr, float b1, "
+          "float b2, float eps, float weight_decay, float clip_norm, int t, float gscale) -> Tensor[]");
     m.def("edt_squared(Tensor labels, int cls, float[] spacing) -> Tensor");
     m.def("hausdorff(Tensor pred, Tensor truth, float[] spacing, int num_classes) -> Tensor");
     m.def("surface_count(Tensor labels, int class_mask) -> Tensor");
@@ -458,6 +515,8 @@ TORCH_LIBRARY_IMPL(mrirt_native, CompositeExplicitAutograd, m) {
     m.impl("inr_forward_f32", &inr_forward_f32);
     m.impl("inr_loss", &inr_loss);
     m.impl("inr_backward", &inr_backward);
+    m.impl("inr_sample_batch", &inr_sample_batch);
+    m.impl("inr_adamw_step", &inr_adamw_step);
     m.impl("edt_squared", &edt_squared);
     m.impl("hausdorff", &hausdorff);
     m.impl("surface_count", &surface_count);

@@ -9,6 +9,9 @@ model_load, predict_volume``: inr/interactive.ipynb cell 5, inr/viewer/brats_vie
   predict_volume(params, case_data, fourier_freqs, chunk) -> (pred,seg) model.py:119-141
   dice_score(pred, true, num_classes) / coverage_dice(pred, true)          model.py:144-161
   siren_apply(params, x, w0=30)                                         neumors_inr.ipynb:1165-1178
+  make_loss_and_grad(num_classes, class_weights, dice_weight, K)        model.py:57-90      (csrc/inr_train.hip)
+  train_inr(config, cases_or_cache, ...) -> (params, state)             train.py:18-259     (csrc/inr_optim.hip)
+  VoxelCache(cases).sample(seed, batch_index, n) / .sample_voxels(...)  dataloader.py:86-96,133-155
 
 ``params`` is the reference's list of ``{"W": [in,out], "b": [out]}`` (SIREN: dict ``l{i}`` ->
 ``{"w","b"}``).  All arithmetic runs in csrc/inr_mlp.hip (bf16 MFMA, fp32 accumulate, split-bf16
@@ -595,3 +598,274 @@ def mlp_autograd(Ws, bs, coords, feats, fourier_freqs: Optional[int] = None) -> 
     c = _dev_f32(coords, dev) if coords is not None else None
     f = _dev_f32(feats, dev) if feats is not None else None
     return _MlpF32.apply(c, f, fourier_freqs, len(Ws), *Ws, *bs)
+
+
+# --- training loop: voxel cache + sampler, clipped AdamW, train_inr (csrc/inr_optim.hip) ---------------------------------------
+ADAMW_B1, ADAMW_B2, ADAMW_EPS, ADAMW_WEIGHT_DECAY = 0.9, 0.999, 1e-8, 1e-4      # optax.adamw's defaults, as train.py uses them
+CHECKPOINT_BASENAME = "checkpoint_step{step:06d}.npz"
+
+
+class VoxelCache:
+    """Device-resident cases of one shape with a counter-based voxel sampler (``StreamingBraTSCache`` + ``sample_batch``,
+    inr/inr/dataloader.py:86-96,133-155).  ``cases``: a list of ``{"mods": (M, H, W, D) float, "seg": (H, W, D) integer}``,
+    NumPy arrays or tensors; the cache keeps the device copies alive and holds the two pointer tables the kernel reads."""
+
+    def __init__(self, cases: Sequence[Dict[str, Any]]):
+        dev = _require_gpu()
+        if len(cases) < 1:
+            raise ValueError("VoxelCache needs at least one case")
+        self.mods = [_dev_f32(c["mods"], dev) for c in cases]
+        self.seg = [_label_volume(c["seg"], dev, "seg") for c in cases]
+        shape = tuple(self.seg[0].shape)
+        M = int(self.mods[0].shape[0])
+        for m, s in zip(self.mods, self.seg):
+            if m.dim() != 4 or tuple(m.shape) != (M, *shape) or tuple(s.shape) != shape:
+                raise ValueError(f"every case must be mods {(M, *shape)} + seg {shape}; got {tuple(m.shape)} + {tuple(s.shape)}")
+        self.n_cases, self.n_modalities, self.vol_shape, self.device = len(cases), M, shape, dev
+        self.cache = [{"mods": m, "seg": s} for m, s in zip(self.mods, self.seg)]
+        self.seg_table = torch.tensor([s.data_ptr() for s in self.seg], dtype=torch.int64, device=dev)
+        self.mods_table = torch.tensor([m.data_ptr() for m in self.mods], dtype=torch.int64, device=dev) if M > 0 else None
+        c = _lib.InrCache()
+        c.mods, c.seg = (self.mods_table.data_ptr() if M > 0 else None), self.seg_table.data_ptr()
+        c.ncases, c.numMods = self.n_cases, M
+        c.hwd[0], c.hwd[1], c.hwd[2] = shape
+        self.desc = c
+
+    def sample(self, seed: int, batch_index: int, n: int):
+        """Micro-batch ``batch_index`` of the stream ``seed`` (``mrirt_inr_sample_batch``): (coords (n, 3) fp32,
+        intensities (n, M) fp32, labels (n,) int32) on the device — the return order of the reference's ``sample_batch``."""
+        dev = self.device
+        coords = torch.empty((int(n), 3), dtype=torch.float32, device=dev)
+        feats = torch.empty((int(n), self.n_modalities), dtype=torch.float32, device=dev)
+        labels = torch.empty(int(n), dtype=torch.int32, device=dev)
+        rc = _lib.lib().mrirt_inr_sample_batch(C.byref(self.desc), int(seed) & (2 ** 64 - 1), int(batch_index) & (2 ** 64 - 1), int(n),
+                                               _ptr(coords), _ptr(feats) if self.n_modalities else None, _ptr(labels), _stream_ptr(None))
+        _lib.check(rc, "mrirt_inr_sample_batch")
+        return coords, feats, labels
+
+    def sample_voxels(self, case_indices, h_coords, w_coords, d_coords):
+        """dataloader.py:86-96: (intensities (N, M) fp32, labels (N,) int16) of the given voxels, by plain indexing."""
+        idx = [torch.as_tensor(np.asarray(v) if not isinstance(v, torch.Tensor) else v).to(self.device).to(torch.int64).reshape(-1)
+               for v in (case_indices, h_coords, w_coords, d_coords)]
+        mods = torch.empty((idx[0].numel(), self.n_modalities), dtype=torch.float32, device=self.device)
+        seg = torch.empty(idx[0].numel(), dtype=torch.int16, device=self.device)
+        for c in range(self.n_cases):                    # case by case: the volumes stay where they are
+            at = torch.nonzero(idx[0] == c).reshape(-1)
+            h, w, d = idx[1][at], idx[2][at], idx[3][at]
+            if self.n_modalities:
+                mods[at] = self.mods[c][:, h, w, d].T
+            seg[at] = self.seg[c][h, w, d]
+        return mods, seg
+
+
+def lr_schedule(peak: float, end: float, warmup_steps: int, decay_steps: int, t: int) -> float:
+    """``optax.warmup_cosine_decay_schedule(0, peak, warmup_steps, decay_steps, end)`` at ``t`` updates already applied, in
+    fp64 (what ``mrirt_inr_lr_schedule`` computes).  ``decay_steps - warmup_steps <= 0`` is refused, as optax asserts."""
+    import math
+    peak, end, warmup, t = float(peak), float(end), int(warmup_steps), int(t)
+    T = int(decay_steps) - warmup
+    if T <= 0:
+        raise ValueError(f"decay_steps ({decay_steps}) must exceed warmup_steps ({warmup_steps})")
+    if not (math.isfinite(peak) and math.isfinite(end) and peak > 0.0 and end >= 0.0):
+        raise ValueError("the schedule needs a finite peak > 0 and a finite end >= 0")
+    if t < warmup:
+        return peak * float(t) / float(warmup)
+    u = float(min(t - warmup, T)) / float(T)
+    alpha = end / peak
+    return peak * ((1.0 - alpha) * (0.5 * (1.0 + math.cos(3.141592653589793 * u))) + alpha)
+
+
+def init_mlp(seed: int, in_dim: int, hidden_dims: Sequence[int], out_dim: int) -> List[Dict[str, np.ndarray]]:
+    """model.py:26-40 with a NumPy generator: Glorot-uniform weights, zero biases (jax's key stream is not reproduced)."""
+    rng = np.random.default_rng(int(seed))
+    dims = [int(in_dim)] + [int(h) for h in hidden_dims] + [int(out_dim)]
+    params = []
+    for a, b in zip(dims[:-1], dims[1:]):
+        lim = np.sqrt(6.0 / (a + b))
+        params.append({"W": rng.uniform(-lim, lim, (a, b)).astype(np.float32), "b": np.zeros(b, np.float32)})
+    return params
+
+
+@dataclass
+class AdamWState:
+    """The flat fp32 master copy of a network with its AdamW moments, on the device, and the number of updates applied."""
+    dims: List[int]
+    w: torch.Tensor
+    b: torch.Tensor
+    mu_w: torch.Tensor
+    mu_b: torch.Tensor
+    nu_w: torch.Tensor
+    nu_b: torch.Tensor
+    step: int = 0
+
+    @staticmethod
+    def from_params(params, dev=None) -> "AdamWState":
+        dev = dev or _require_gpu()
+        layers = _layers(params) if not isinstance(params[0]["W"], torch.Tensor) else [(p["W"], p["b"]) for p in params]
+        Ws, bs = [_dev_f32(W, dev) for W, _ in layers], [_dev_f32(b, dev) for _, b in layers]
+        dims = _param_dims(Ws, bs)
+        w, b = torch.cat([W.reshape(-1) for W in Ws]), torch.cat([x.reshape(-1) for x in bs])
+        return AdamWState(dims, w, b, torch.zeros_like(w), torch.zeros_like(b), torch.zeros_like(w), torch.zeros_like(b), 0)
+
+    def params(self) -> List[Dict[str, np.ndarray]]:
+        return [{"W": g["W"].cpu().numpy().copy(), "b": g["b"].cpu().numpy().copy()} for g in _split_grads(self.w, self.b, self.dims)]
+
+    def c_state(self) -> _lib.InrTrainState:
+        return _lib.InrTrainState(*[t.data_ptr() for t in (self.w, self.b, self.mu_w, self.mu_b, self.nu_w, self.nu_b)])
+
+
+def adamw_step(st: AdamWState, gw: torch.Tensor, gb: torch.Tensor, lr: float, gscale: float = 1.0, clip_norm: float = 0.0,
+               b1: float = ADAMW_B1, b2: float = ADAMW_B2, eps: float = ADAMW_EPS, weight_decay: float = ADAMW_WEIGHT_DECAY) -> torch.Tensor:
+    """``mrirt_inr_adamw_step`` in place on ``st`` (update number ``st.step + 1``; ``st.step`` is advanced): clip by the
+    global norm of ``gscale`` x (gw, gb), then AdamW with the given rate.  Returns the fp64 device tensor [norm, clip factor]."""
+    lib = _lib.lib()
+    n = st.w.numel() + st.b.numel()
+    nbytes = int(lib.mrirt_inr_adamw_scratch_bytes(n))
+    scratch = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=st.w.device)
+    gnorm = torch.empty(2, dtype=torch.float64, device=st.w.device)
+    hp = _lib.AdamW(lr, b1, b2, eps, weight_decay, clip_norm)
+    rc = lib.mrirt_inr_adamw_step(_ptr(st.w), _ptr(st.b), _ptr(gw), _ptr(gb), _ptr(st.mu_w), _ptr(st.mu_b), _ptr(st.nu_w), _ptr(st.nu_b),
+                                  st.w.numel(), st.b.numel(), C.byref(hp), int(st.step), float(gscale), _ptr(gnorm), _ptr(scratch), nbytes,
+                                  _stream_ptr(None))
+    _lib.check(rc, "mrirt_inr_adamw_step")
+    st.step += 1
+    return gnorm
+
+
+def train_cfg(micro_batch: int, accum: int, seed: int, class_weights, dice_weight: float, peak_lr: float, min_lr: float,
+              warmup_steps: int, decay_steps: int, clip_norm: float, b1: float = ADAMW_B1, b2: float = ADAMW_B2, eps: float = ADAMW_EPS,
+              weight_decay: float = ADAMW_WEIGHT_DECAY) -> _lib.InrTrainCfg:
+    c = _lib.InrTrainCfg()
+    c.microBatch, c.accum, c.warmupSteps, c.decaySteps, c.seed = int(micro_batch), int(accum), int(warmup_steps), int(decay_steps), int(seed) & (2 ** 64 - 1)
+    c.peakLr, c.minLr, c.diceWeight = float(peak_lr), float(min_lr), float(dice_weight)
+    cw = [float(np.float32(v)) for v in class_weights]
+    if len(cw) > 16:
+        raise ValueError("at most 16 classes")
+    for k, v in enumerate(cw):
+        c.classWeights[k] = v
+    c.adamw = _lib.AdamW(0.0, b1, b2, eps, weight_decay, clip_norm)
+    return c
+
+
+def train_run(desc: _lib.InrDesc, cache: VoxelCache, cfg: _lib.InrTrainCfg, st: AdamWState, steps: int, scratch: Optional[torch.Tensor] = None):
+    """``mrirt_inr_train_run``: ``steps`` optimiser steps from ``st.step`` on, enqueued in one call without a host
+    synchronisation.  Returns the device tensor history (steps, accum, 1 + 2 C): loss, CE per class, Dice per class of every
+    micro-batch.  ``st`` is updated in place and ``st.step`` advanced."""
+    lib = _lib.lib()
+    nbytes = int(lib.mrirt_inr_train_run_scratch_bytes(C.byref(desc), C.byref(cache.desc), C.byref(cfg)))
+    if nbytes <= 0:
+        raise ValueError("train_run: unsupported network / cache / configuration (Fourier ReLU kind over the cache's modalities, "
+                         "accum >= 1, decay_steps > warmup_steps, finite hyper-parameters)")
+    if scratch is None or scratch.numel() < nbytes:
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=st.w.device)
+    hist = torch.empty((int(steps), int(cfg.accum), 1 + 2 * int(desc.outDim)), dtype=torch.float32, device=st.w.device)
+    cs = st.c_state()
+    rc = lib.mrirt_inr_train_run(C.byref(desc), C.byref(cache.desc), C.byref(cfg), C.byref(cs), int(st.step), int(steps), _ptr(hist),
+                                 _ptr(scratch), scratch.numel(), _stream_ptr(None))
+    _lib.check(rc, "mrirt_inr_train_run")
+    st.step += int(steps)
+    return hist
+
+
+def _load_resume(path) -> Tuple[List[Dict[str, np.ndarray]], Optional[Dict[str, np.ndarray]]]:
+    """A checkpoint's parameters — the periodic W_i / b_i layout read directly (no pickle), anything else through
+    ``model_load`` — and, when the optimiser file this loop writes beside it exists, the moments and the step count."""
+    path = pathlib.Path(path).expanduser()
+    if not path.is_file():
+        raise FileNotFoundError(f"resume_from: no checkpoint at {path}")
+    with np.load(str(path)) as z:
+        names = list(z.files)
+        flat = bool(names) and all(n.startswith(("W_", "b_")) for n in names)
+        if flat:
+            count = sum(n.startswith("W_") for n in names)
+            params = [{"W": np.asarray(z[f"W_{i}"], np.float32), "b": np.asarray(z[f"b_{i}"], np.float32)} for i in range(count)]
+    if not flat:
+        params, _ = model_load(path)
+        params = [{"W": W, "b": b} for W, b in _layers(params)]
+    opt_path = path.with_name(path.stem + "_opt.npz")
+    opt = None
+    if opt_path.is_file():
+        with np.load(str(opt_path)) as z:
+            opt = {k: np.asarray(z[k]) for k in z.files}
+    return params, opt
+
+
+def train_inr(config: Dict[str, Any], cases_or_cache, val_cases=None, params=None, resume_from=None, log=None, save_path=None):
+    """inr/inr/train.py:18-259 on the GPU with the reference's config keys (GLOBAL_BATCH_SIZE, MICRO_BATCH_SIZE, FOURIER_FREQS,
+    HIDDEN_DIMS, LR, MIN_LR, WARMUP_STEPS, TRAIN_STEPS, RNG_SEED, NUM_CLASSES, DICE_WEIGHT, CLASS_WEIGHTS, CLIP_NORM,
+    CHECKPOINT_EVERY_STEPS): ``accum = ceil(global / micro)`` micro-batches per update, clip_by_global_norm + AdamW under the
+    warm-up / cosine schedule, all inside ``mrirt_inr_train_run`` — one call per chunk of steps, a chunk ending at every
+    checkpoint step, and one read-back of the chunk's history.
+
+    ``cases_or_cache``: a ``VoxelCache`` or the list of cases to build one from.  ``params``: initial parameters (default
+    ``init_mlp(RNG_SEED, ...)``).  ``save_path``: a directory; only then ``checkpoint_step{step:06d}.npz`` (``W_i`` / ``b_i``,
+    the reference's periodic layout) is written every CHECKPOINT_EVERY_STEPS steps, with the optimiser moments and the step
+    in ``checkpoint_step{step:06d}_opt.npz`` beside it.  ``resume_from``: such a file (with the moments beside it the run
+    continues at its step and reproduces the uninterrupted run bit for bit; without them it restarts the schedule from the
+    loaded parameters, as the reference does) or a ``model_load`` checkpoint.  ``log(step, metrics)`` is called per step.
+    Returns ``(params, state)``: the reference's list of ``{"W", "b"}`` (NumPy) and a dict with ``loss_history``,
+    ``dice_history`` / ``ce_history`` (per class), the caches, ``vol_shape`` and ``opt`` (the ``AdamWState``)."""
+    g, micro = int(config["GLOBAL_BATCH_SIZE"]), int(config["MICRO_BATCH_SIZE"])
+    K, hidden_dims = int(config["FOURIER_FREQS"]), [int(h) for h in config["HIDDEN_DIMS"]]
+    warmup, train_steps = int(config["WARMUP_STEPS"]), int(config["TRAIN_STEPS"])
+    nc, seed = int(config["NUM_CLASSES"]), int(config["RNG_SEED"])
+    every = int(config.get("CHECKPOINT_EVERY_STEPS", 200))
+    if micro < 1 or g < 1 or train_steps < 1 or every < 1:
+        raise ValueError("GLOBAL_BATCH_SIZE, MICRO_BATCH_SIZE, TRAIN_STEPS and CHECKPOINT_EVERY_STEPS must be positive")
+    accum = (g + micro - 1) // micro
+    decay_steps = max(1, train_steps - warmup)
+    lr_schedule(float(config["LR"]), float(config["MIN_LR"]), warmup, decay_steps, 0)          # refuses T <= 0 before any work
+    cache = cases_or_cache if isinstance(cases_or_cache, VoxelCache) else VoxelCache(cases_or_cache)
+    val_cache = None if val_cases is None else (val_cases if isinstance(val_cases, VoxelCache) else VoxelCache(val_cases))
+    in_dim = 3 + 6 * K + cache.n_modalities
+    opt = None
+    if resume_from is not None:
+        params, opt = _load_resume(resume_from)
+    elif params is None:
+        params = init_mlp(seed, in_dim, hidden_dims, nc)
+    st = AdamWState.from_params(params, cache.device)
+    if st.dims != [in_dim] + hidden_dims + [nc]:
+        raise ValueError(f"the parameters have layer widths {st.dims}, the config asks for {[in_dim] + hidden_dims + [nc]}")
+    if opt is not None:
+        for k in ("mu_w", "mu_b", "nu_w", "nu_b"):
+            getattr(st, k).copy_(torch.from_numpy(np.asarray(opt[k], np.float32)))
+        st.step = int(opt["step"])
+    desc = train_desc(st.dims, K, cache.n_modalities)
+    cfg = train_cfg(micro, accum, seed, config["CLASS_WEIGHTS"], float(config["DICE_WEIGHT"]), float(config["LR"]), float(config["MIN_LR"]),
+                    warmup, decay_steps, float(config["CLIP_NORM"]))
+    if save_path is not None:
+        save_path = pathlib.Path(save_path)
+        save_path.mkdir(parents=True, exist_ok=True)
+    loss_history: List[float] = []
+    dice_history: List[List[float]] = [[] for _ in range(nc)]
+    ce_history: List[List[float]] = [[] for _ in range(nc)]
+    nbytes = int(_lib.lib().mrirt_inr_train_run_scratch_bytes(C.byref(desc), C.byref(cache.desc), C.byref(cfg)))
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=cache.device) if nbytes > 0 else None      # one buffer for every chunk
+    while st.step < train_steps:
+        first = st.step
+        steps = min(train_steps, (first // every + 1) * every, first + 4096) - first
+        h = train_run(desc, cache, cfg, st, steps, scratch).cpu().numpy().astype(np.float64).mean(axis=1)     # per-step means
+        for k in range(steps):
+            loss_history.append(float(h[k, 0]))
+            for c in range(nc):
+                ce_history[c].append(float(h[k, 1 + c]))
+                dice_history[c].append(float(h[k, 1 + nc + c]))
+            if log is not None:
+                m = {"train/loss": float(h[k, 0]), "train/step": first + k + 1, "train/dice_mean": float(h[k, 1 + nc:].mean()),
+                     "train/ce_mean": float(h[k, 1:1 + nc].mean())}
+                for c in range(nc):
+                    m[f"train/dice_class_{c}"], m[f"train/ce_class_{c}"] = float(h[k, 1 + nc + c]), float(h[k, 1 + c])
+                log(first + k + 1, m)
+        if save_path is not None and st.step % every == 0:
+            flat = {}
+            for i, layer in enumerate(st.params()):
+                flat[f"W_{i}"], flat[f"b_{i}"] = layer["W"], layer["b"]
+            ck = save_path / CHECKPOINT_BASENAME.format(step=st.step)
+            np.savez_compressed(ck, **flat)
+            np.savez_compressed(ck.with_name(ck.stem + "_opt.npz"), step=np.int64(st.step),
+                                **{k: getattr(st, k).cpu().numpy() for k in ("mu_w", "mu_b", "nu_w", "nu_b")})
+    out = st.params()
+    state = {"params": out, "train_cache": cache, "val_cache": val_cache, "vol_shape": cache.vol_shape, "loss_history": loss_history,
+             "dice_history": dice_history, "ce_history": ce_history, "best_val_dice": None, "best_step": None, "save_path": save_path,
+             "checkpoint_periodic_basename": CHECKPOINT_BASENAME, "opt": st}
+    return out, state

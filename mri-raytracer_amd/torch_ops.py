@@ -16,7 +16,7 @@ C++ extension (``load_native()`` -> ``torch.ops.mrirt_native.*``, csrc/torch_bin
 from __future__ import annotations
 
 import ctypes as C
-from typing import Any, Mapping, Optional, Sequence, Tuple
+from typing import Any, List, Mapping, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -565,3 +565,70 @@ def inr_backward(weights: torch.Tensor, dlogits: torch.Tensor, scratch: torch.Te
 def _(weights, dlogits, scratch, kind, num_layers, in_dim, out_dim, hidden, fourier_freqs, num_mods, n):
     _, _, nw, nb = _train_desc(kind, num_layers, in_dim, out_dim, hidden, fourier_freqs, num_mods, n)
     return (torch.empty(nw, dtype=torch.float32, device=weights.device), torch.empty(nb, dtype=torch.float32, device=weights.device))
+
+
+# --- INR training loop: voxel sampler and clipped AdamW (csrc/inr_optim.hip) ------------------------------------------------
+def _u64(v: int) -> int:
+    return int(v) & 0xFFFFFFFFFFFFFFFF
+
+
+@torch.library.custom_op("mrirt::inr_sample_batch", mutates_args=())
+def inr_sample_batch(mods_table: Optional[torch.Tensor], seg_table: torch.Tensor, num_mods: int, h: int, w: int, d: int, seed: int,
+                     batch_index: int, n: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(coords fp32 [n, 3], feats fp32 [n, num_mods], labels int32 [n]) of mrirt_inr_sample_batch.  ``mods_table`` /
+    ``seg_table`` are int64 device tensors of per-case device addresses (fp32 [num_mods, h, w, d] and int16 [h, w, d] volumes,
+    which the caller keeps alive); ``seed`` and ``batch_index`` are taken modulo 2^64."""
+    st = _dev_flat(seg_table, torch.int64, "seg_table")
+    mt = _dev_flat(mods_table, torch.int64, "mods_table")
+    if st.numel() < 1 or (num_mods > 0 and (mt is None or mt.numel() != st.numel())):
+        raise ValueError("seg_table must hold one address per case, and mods_table as many when num_mods > 0")
+    dev = _one_device([("seg_table", st), ("mods_table", mt)])
+    c = _lib.InrCache()
+    c.mods, c.seg, c.ncases, c.numMods = (mt.data_ptr() if num_mods > 0 else None), st.data_ptr(), st.numel(), num_mods
+    c.hwd[0], c.hwd[1], c.hwd[2] = h, w, d
+    with torch.cuda.device(dev):
+        coords = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        feats = torch.empty((n, num_mods), dtype=torch.float32, device=dev)
+        labels = torch.empty(n, dtype=torch.int32, device=dev)
+        rc = _lib.lib().mrirt_inr_sample_batch(C.byref(c), _u64(seed), _u64(batch_index), int(n), _ptr(coords),
+                                               _ptr(feats) if num_mods > 0 else None, _ptr(labels), _stream())
+    _lib.check(rc, "mrirt_inr_sample_batch")
+    return coords, feats, labels
+
+
+@inr_sample_batch.register_fake
+def _(mods_table, seg_table, num_mods, h, w, d, seed, batch_index, n):
+    dev = seg_table.device
+    return (torch.empty((n, 3), dtype=torch.float32, device=dev), torch.empty((n, num_mods), dtype=torch.float32, device=dev),
+            torch.empty(n, dtype=torch.int32, device=dev))
+
+
+@torch.library.custom_op("mrirt::inr_adamw_step", mutates_args=())
+def inr_adamw_step(w: torch.Tensor, b: torch.Tensor, gw: torch.Tensor, gb: torch.Tensor, mu_w: torch.Tensor, mu_b: torch.Tensor,
+                   nu_w: torch.Tensor, nu_b: torch.Tensor, lr: float, b1: float, b2: float, eps: float, weight_decay: float,
+                   clip_norm: float, t: int, gscale: float) -> List[torch.Tensor]:
+    """[w, b, mu_w, mu_b, nu_w, nu_b, gnorm] after update number t + 1 of mrirt_inr_adamw_step on copies of the flat fp32
+    parameters and moments (the arguments are not changed); gnorm fp64 [2] = the global gradient norm and the clip factor."""
+    ten = [_dev_flat(x, torch.float32, k) for k, x in (("w", w), ("b", b), ("gw", gw), ("gb", gb), ("mu_w", mu_w), ("mu_b", mu_b),
+                                                        ("nu_w", nu_w), ("nu_b", nu_b))]
+    nw, nb = ten[0].numel(), ten[1].numel()
+    if any(x.numel() != nw for x in ten[2::2]) or any(x.numel() != nb for x in ten[3::2]):
+        raise ValueError("gradients and moments must have the sizes of w and b")
+    dev = _one_device([("w", ten[0])] + [("arg", x) for x in ten[1:]])
+    lib = _lib.lib()
+    hp = _lib.AdamW(lr, b1, b2, eps, weight_decay, clip_norm)
+    with torch.cuda.device(dev):
+        ow, ob, omw, omb, onw, onb = (ten[i].clone() for i in (0, 1, 4, 5, 6, 7))
+        nbytes = int(lib.mrirt_inr_adamw_scratch_bytes(nw + nb))
+        scratch = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+        gnorm = torch.empty(2, dtype=torch.float64, device=dev)
+        rc = lib.mrirt_inr_adamw_step(_ptr(ow), _ptr(ob), _ptr(ten[2]), _ptr(ten[3]), _ptr(omw), _ptr(omb), _ptr(onw), _ptr(onb), nw, nb,
+                                      C.byref(hp), _u64(t), float(gscale), _ptr(gnorm), _ptr(scratch), nbytes, _stream())
+    _lib.check(rc, "mrirt_inr_adamw_step")
+    return [ow, ob, omw, omb, onw, onb, gnorm]
+
+
+@inr_adamw_step.register_fake
+def _(w, b, gw, gb, mu_w, mu_b, nu_w, nu_b, lr, b1, b2, eps, weight_decay, clip_norm, t, gscale):
+    return [torch.empty_like(w), torch.empty_like(b), torch.empty_like(mu_w), torch.empty_like(mu_b), torch.empty_like(nu_w),
+            torch.empty_like(nu_b), torch.empty(2, dtype=torch.float64, device=w.device)]

@@ -2,10 +2,11 @@
 """Fit a small Fourier/ReLU INR to the synthetic label volume with the library's own training step — the optimisation demo
 (the reference's docs/Goals.md "Differentiability Proof": a gradient from a loss to the MLP's weights, then a fit).
 
-Every step draws a random batch of voxels, runs ``mrirt.inr.make_loss_and_grad`` (fp32 forward, the reference's CE + soft
-Dice loss and the weight gradients, all in csrc/inr_train.hip) and hands the gradients to ``torch.optim.AdamW``.  Loss and
-per-class Dice of the whole volume are printed before and after; the fitted weights then go through ``pack_mlp`` and
-``predict_volume``, the bf16 inference path, whose Dice against the labels is the last line.
+The fit is ``mrirt.inr.train_inr``: every step draws a batch of voxels from the device-resident case (the counter-based
+sampler), runs the fp32 forward, the reference's CE + soft Dice loss and the weight gradients (csrc/inr_train.hip) and applies
+AdamW (csrc/inr_optim.hip), all enqueued by ``mrirt_inr_train_run`` in chunks of 100 steps — a constant learning rate, no
+clipping.  Loss and per-class Dice of the whole volume are printed before and after; the fitted weights then go through
+``pack_mlp`` and ``predict_volume``, the bf16 inference path, whose Dice against the labels is the last line.
 
     python tools/inr_fit.py [--size 48] [--steps 300] [--batch 4096] [--hidden 64] [--layers 4] [--freqs 4] [--lr 3e-3]
 """
@@ -46,33 +47,24 @@ def main():
     counts = np.bincount(seg.reshape(-1), minlength=nc).astype(np.float64)
     cw = (counts.sum() / (nc * np.maximum(counts, 1.0))).astype(np.float32)          # inverse-frequency class weights
 
-    rng = np.random.default_rng(args.seed)
-    dims = [3 + 6 * K + 4] + [args.hidden] * args.layers + [nc]
-    params = []
-    for a, b in zip(dims[:-1], dims[1:]):                # init_mlp of the reference: Glorot weights, zero biases
-        lim = np.sqrt(6.0 / (a + b))
-        params.append({"W": torch.from_numpy(rng.uniform(-lim, lim, (a, b)).astype(np.float32)).to(dev),
-                       "b": torch.zeros(b, dtype=torch.float32, device=dev)})
-    flat = [p[k] for p in params for k in ("W", "b")]
-    opt = torch.optim.AdamW(flat, lr=args.lr, weight_decay=0.0)
+    params = [{k: torch.from_numpy(v).to(dev) for k, v in p.items()} for p in inr.init_mlp(args.seed, 3 + 6 * K + 4, [args.hidden] * args.layers, nc)]
     step = inr.make_loss_and_grad(nc, cw, args.dice_weight, K)
+    config = dict(GLOBAL_BATCH_SIZE=args.batch, MICRO_BATCH_SIZE=args.batch, FOURIER_FREQS=K, HIDDEN_DIMS=[args.hidden] * args.layers, LR=args.lr,
+                  MIN_LR=args.lr, WARMUP_STEPS=0, TRAIN_STEPS=args.steps, RNG_SEED=args.seed, NUM_CLASSES=nc, DICE_WEIGHT=args.dice_weight,
+                  CLASS_WEIGHTS=[float(v) for v in cw], CLIP_NORM=float("inf"), CHECKPOINT_EVERY_STEPS=100)
 
     def whole_volume(tag):
         (loss, aux), _ = step(params, coords, feats, labels)
         print(f"{tag}: loss {float(loss):.4f}  soft dice per class {[round(float(v), 4) for v in aux['dice_per_class'].cpu()]}"
               f"  ce per class {[round(float(v), 4) for v in aux['ce_per_class'].cpu()]}")
     whole_volume("before")
-    gen = torch.Generator(device=dev).manual_seed(args.seed)
-    for it in range(args.steps):
-        idx = torch.randint(0, coords.shape[0], (args.batch,), device=dev, generator=gen)
-        (loss, _), grads = step(params, coords[idx], feats[idx], labels[idx])
-        for p, g in zip(params, grads):
-            p["W"].grad, p["b"].grad = g["W"], g["b"]
-        opt.step()
-        if (it + 1) % 100 == 0:
-            print(f"step {it + 1}: batch loss {float(loss):.4f}")
+
+    def log(it, m):
+        if it % 100 == 0:
+            print(f"step {it}: batch loss {m['train/loss']:.4f}")
+    host, _ = inr.train_inr(config, [{"mods": mods, "seg": seg}], params=[{k: v.cpu().numpy() for k, v in p.items()} for p in params], log=log)
+    params = [{k: torch.from_numpy(v).to(dev) for k, v in p.items()} for p in host]
     whole_volume("after")
-    host = [{"W": p["W"].cpu().numpy(), "b": p["b"].cpu().numpy()} for p in params]
     net = inr.pack_mlp(host, inr.KIND_FOURIER_RELU, K, 4)
     pred, _ = inr.predict_volume(host, {"mods": mods, "seg": seg}, K, net=net)
     dice = inr.dice_score(pred, torch.from_numpy(seg).to(dev), nc)
