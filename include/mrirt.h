@@ -151,7 +151,9 @@ typedef struct MrirtRenderExt {
 
 /* Argument checks shared by every K1 entry point (MRIRT_ERR_ARG, nothing is launched): stepSize must be a
  * finite positive number that still advances t in fp32 at the far end of the box (t + stepSize > t) and may
- * not cut the box diagonal into more than 2^20 steps; voxelSize finite and > 0; volMin / eye finite.  The
+ * not cut the box diagonal into more than 2^20 steps; voxelSize finite and > 0; volMin / eye / U / V / W finite, fovY
+ * finite in perspective mode (a camera that is not finite makes NaN rays); intensityAlpha not a NaN (the strict exp
+ * would turn it into an opacity of 1 where the shader's is NaN).  The
  * reference's UI clamps its slider to >= 0.001 (inr/viewer/brats_viewer.py:168); the shader itself would
  * spin.  K2: stepCount finite and <= 2^20, near / far finite.  K3: maxSteps <= 2^20.                      */
 

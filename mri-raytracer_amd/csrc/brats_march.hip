@@ -746,6 +746,14 @@ int prepare(const MrirtBratsParams* p, const MrirtRenderExt* ext, const void* co
         const float tFar = (float)tMax;
         if (!isfinite(tFar) || !(tFar + h > tFar)) return MRIRT_ERR_ARG;          // t += stepSize must advance
         if (sqrt(diag2) / (double)h > (double)kMaxStepsPerRay) return MRIRT_ERR_ARG;
+        // The strict exp clamps its argument with fmax / fmin, which drop a NaN (exp_f64_to_f32: NaN -> exp(-200) = 0, where the
+        // oracle's (float)exp((double)NaN) is NaN).  Its argument is -(val * intensityAlpha) * stepSize with val in (0, 1] and
+        // the step finite, so only a NaN intensityAlpha can put a NaN there: refused here rather than rendered differently.
+        if (isnan(p->intensityAlpha)) return MRIRT_ERR_ARG;
+        // ... and a camera that is not finite makes NaN rays (every pIdx a NaN): nothing to render, refused like the other
+        // parameters that are not finite (fovY makes the rays in perspective mode only)
+        if (!(ext && ext->cameraMode == 1u) && !isfinite(p->fovY)) return MRIRT_ERR_ARG;
+        for (int k = 0; k < 3; ++k) if (!isfinite(p->U[k]) || !isfinite(p->V[k]) || !isfinite(p->W[k])) return MRIRT_ERR_ARG;
     }
     fill_camera(a.cam, p->eye, p->U, p->V, p->W, p->fovY, p->imageSize[0], p->imageSize[1], ext, false);
     // Workgroup = one 8 x 8 packet (64 threads: a finished packet's wave slot refills at once) — except on VGA grids, where

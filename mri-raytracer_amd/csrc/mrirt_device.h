@@ -36,7 +36,9 @@ struct UDiv { float d, r; uint32_t exact; };
 
 // Correctly rounded fp32 exp via fp64: 2^k * P13(x - k ln2).  Same "round a <1-ulp fp64 value
 // once" contract as (float)exp((double)x) on the host, at a third of OCML's instruction count
-// (the argument here is -(val*alpha)*dt: no need for the full double domain).
+// (the argument here is -(val*alpha)*dt: no need for the full double domain).  Domain: every fp32 x that is not a NaN,
+// +-inf and results that are fp32 denormals included; the clamp drops a NaN (fmax / fmin: exp(NaN) = exp(-200) = 0 where the
+// host's is NaN), which is why prepare() refuses a NaN intensityAlpha, the one way a NaN can reach the argument.
 // The sixteen fp64 constants come in through the kernel arguments (ExpConsts, filled by the host), i.e. they
 // sit in SGPR pairs and feed v_fma_f64 directly: as literals each one costs a v_mov_b64 into a VGPR pair
 // per use (a 64-bit literal cannot be an operand), ten extra VALU instructions per exp in the march loop.
@@ -107,15 +109,21 @@ __device__ __forceinline__ float exp_f64_to_f32(float xf) {
 }
 
 template <> struct M<true> {
-    // bit-faithful to oracle_c.c / oracle_np.py: unfused fp32 in the written order; divisions
-    // and exp are correctly rounded by construction
+    // bit-faithful to oracle_c.c / oracle_np.py: unfused fp32 in the written order; divisions and exp are correctly rounded
+    // ON THE DOMAINS STATED BELOW (each function is swept on its own against exact references by
+    // tests/test_gpu_math_primitives.py; DESIGN.md section 2 lists the call sites and why they stay inside)
     static __device__ __forceinline__ float lerp(float a, float b, float t) { return a + t * (b - a); }
     static __device__ __forceinline__ float exp(float x, const ExpConsts& e) { return exp_f64_to_f32(x, e); }
     static __device__ __forceinline__ float exp_lit(float x) { return exp_f64_to_f32(x); }
     static __device__ __forceinline__ float exp_small(float x, const ExpConsts& e) { return exp_small_f64_to_f32(x, e); }
     static __device__ __forceinline__ float exp_small_lit(float x) { return exp_small_f64_to_f32(x); }
-    // x / u.d, IEEE-exact in 3 instructions (Markstein: q = RN(x r); e = x - q d exactly by FMA;
-    // RN(q + e r) is the correctly rounded quotient when r = RN(1/d))
+    // x / u.d in 3 instructions (Markstein: q = RN(x r); e = x - q d exactly by FMA; RN(q + e r) is the correctly rounded
+    // quotient when r = RN(1/d)).  It IS the IEEE quotient, bit for bit, for u.exact and
+    //   x = +0 (or -0 over d < 0), or |x| >= 2^-100 with 2^-126 <= |x / d| <= 2^126
+    // (e is a multiple of 2^(ex - 47): representable from ex >= -102; q and the quotient must be normal; x r must not overflow).
+    // Outside: -0 over d > 0 gives +0; a numerator below 2^-102 or a subnormal quotient may be one ulp off (the residual
+    // underflows); a finite quotient that overflows gives NaN (inf - inf) here and the infinity in divu_data.  !u.exact (d or
+    // 1/d not normal, significand of d all ones) takes the true division.
     static __device__ __forceinline__ float divu(float x, const UDiv& u) {
         if (!u.exact) return x / u.d;
         const float q = x * u.r;
@@ -157,8 +165,11 @@ template <> struct M<false> {
     static __device__ __forceinline__ float mad(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 };
 
-// v_med3_f32: one instruction; with a NaN input it returns min3 of the others, i.e. lo — the same
-// result as fminf(fmaxf(NaN, lo), hi) and as HLSL saturate(NaN) = 0 (requires lo <= hi).
+// v_med3_f32: one instruction; equals fminf(fmaxf(x, lo), hi) (requires lo <= hi; -0 < +0) for every x, with IEEE 754-2008's
+// maxNum / minNum for a NaN: a QUIET NaN — the only kind arithmetic produces — gives lo, the same as HLSL's clamp and
+// saturate(NaN) = 0; a SIGNALLING NaN (it can only come out of memory) gives hi, since maxNum(sNaN, lo) is a quiet NaN and
+// minNum(qNaN, hi) = hi.  Both measured on the MI355X for every NaN of tests/test_gpu_math_primitives.py, with bounds from
+// memory and with literal ones.  satf's constant bounds compile to v_max_f32 with the clamp modifier: 0 for every NaN.
 __device__ __forceinline__ float clampf(float x, float lo, float hi) { return __builtin_amdgcn_fmed3f(x, lo, hi); }
 __device__ __forceinline__ float satf(float x) { return __builtin_amdgcn_fmed3f(x, 0.0f, 1.0f); }
 MRIRT_HD float dot3(float ax, float ay, float az, float bx, float by, float bz) {

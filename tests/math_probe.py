@@ -1,0 +1,318 @@
+"""Build and bind tests/native/math_probe.hip: one entry point per device math primitive (TEST INFRASTRUCTURE, not part of
+libmrirt.so).  ``build()`` cross-compiles it for gfx950 with exactly the product's flags and include path
+(``mrirt._lib.HIPCC_FLAGS``: the STRICT contract rests on ``-O3 -ffp-contract=off``) into
+``tests/native/_build/libmrirt_probe.so`` and rebuilds when a source is newer, as ``mrirt._lib.build()`` does.  The host
+entries (``make_udiv``, ``exp_consts``, ``fill_camera``, ``fill_k1args``) need no GPU; the device entries take torch tensors
+on the current device."""
+from __future__ import annotations
+
+import ctypes as C
+import importlib
+import pathlib
+import subprocess
+from typing import Optional
+
+import numpy as np
+
+ROOT = pathlib.Path(__file__).resolve().parent.parent
+SRC = ROOT / "tests" / "native" / "math_probe.hip"
+OUT = ROOT / "tests" / "native" / "_build"
+SO_PATH = OUT / "libmrirt_probe.so"
+
+# probe_composite's combo index: bit 0 STRICT, bit 1 SHADE, bit 2 GAMMA1
+COMBOS = [(strict, shade, gamma1) for gamma1 in (False, True) for shade in (False, True) for strict in (False, True)]
+K1_FIELDS = ("ww", "wl", "gamma", "wsum", "intensityAlpha", "stepSize", "ka", "kd", "ks", "gradEps", "specPow2", "hx", "hy", "hz")
+
+
+def _mlib():
+    return importlib.import_module("mri-raytracer_amd._lib")
+
+
+def _sources():
+    m = _mlib()
+    return [SRC] + m._headers()
+
+
+def build(force: bool = False, verbose: bool = False) -> pathlib.Path:
+    m = _mlib()
+    if not force and SO_PATH.exists() and all(p.stat().st_mtime <= SO_PATH.stat().st_mtime for p in _sources()):
+        return SO_PATH
+    OUT.mkdir(parents=True, exist_ok=True)
+    cmd = [m._hipcc(), *m.HIPCC_FLAGS, f"-I{m.INCLUDE}", str(SRC), "-o", str(SO_PATH)]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    if verbose or r.returncode != 0:
+        print(" ".join(cmd))
+        print(r.stdout + r.stderr)
+    if r.returncode != 0:
+        SO_PATH.unlink(missing_ok=True)
+        raise RuntimeError("hipcc failed on tests/native/math_probe.hip")
+    return SO_PATH
+
+
+_LIB: Optional[C.CDLL] = None
+
+
+def lib() -> C.CDLL:
+    global _LIB
+    if _LIB is None:
+        l = C.CDLL(str(build()))
+        vp, i64, i32, u32, f32 = C.c_void_p, C.c_int64, C.c_int, C.c_uint32, C.c_float
+        l.probe_make_udiv.argtypes = [vp, vp, vp, i64]
+        l.probe_make_udiv.restype = None
+        l.probe_fill_exp_consts.argtypes = [vp]
+        l.probe_fill_exp_consts.restype = None
+        l.probe_fill_camera.argtypes = [vp, vp, vp, vp, f32, u32, u32, i32, u32, f32, i32, vp]
+        l.probe_fill_camera.restype = None
+        l.probe_sizeof.argtypes = [i32]
+        l.probe_sizeof.restype = u32
+        l.probe_fill_k1args.argtypes = [vp, i64, vp]
+        l.probe_fill_k1args.restype = None
+        l.probe_divu.argtypes = [i32, i32, vp, vp, vp, vp, vp, i64, vp]
+        l.probe_exp.argtypes = [i32, vp, vp, i64, vp]
+        l.probe_pow.argtypes = [vp, vp, vp, i64, vp]
+        l.probe_clampf.argtypes = [vp, vp, vp, vp, i64, vp]
+        l.probe_satf.argtypes = [vp, vp, i64, vp]
+        l.probe_clampf_k3.argtypes = [vp, vp, i64, vp]
+        l.probe_lerp.argtypes = [i32, vp, vp, vp, vp, i64, vp]
+        l.probe_lerp2.argtypes = [i32, vp, vp, vp, vp, i64, vp]
+        l.probe_trilerp2.argtypes = [i32, vp, vp, vp, i64, vp]
+        l.probe_primary_ray.argtypes = [vp, vp, vp, vp]
+        l.probe_store_rgba.argtypes = [i32, vp, vp, i64, i64, vp]
+        l.probe_wave_count.argtypes = [vp, vp, i64, vp]
+        l.probe_composite.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]
+        l.probe_fill_locate_args.argtypes = [vp, i64, vp]
+        l.probe_fill_locate_args.restype = None
+        l.probe_locate.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]
+        for fn in ("probe_divu", "probe_exp", "probe_pow", "probe_clampf", "probe_clampf_k3", "probe_satf", "probe_lerp", "probe_lerp2", "probe_trilerp2",
+                   "probe_primary_ray", "probe_store_rgba", "probe_wave_count", "probe_composite", "probe_locate"):
+            getattr(l, fn).restype = i32
+        _LIB = l
+    return _LIB
+
+
+# ---- host entries --------------------------------------------------------------------------------------------------
+def _np_ptr(a: np.ndarray) -> int:
+    assert a.flags["C_CONTIGUOUS"]
+    return a.ctypes.data
+
+
+def make_udiv(d):
+    """The product's make_udiv for every divisor: (r, exact) as float32 / uint32 arrays."""
+    d = np.ascontiguousarray(d, dtype=np.float32).reshape(-1)
+    r = np.empty_like(d)
+    exact = np.empty(d.size, dtype=np.uint32)
+    lib().probe_make_udiv(_np_ptr(d), _np_ptr(r), _np_ptr(exact), d.size)
+    return r, exact
+
+
+def exp_consts() -> np.ndarray:
+    """fill_exp_consts: log2e, ln2hi, ln2lo, c[0..12] (float64)."""
+    out = np.empty(16, dtype=np.float64)
+    lib().probe_fill_exp_consts(_np_ptr(out))
+    return out
+
+
+CAMERA_DTYPE = np.dtype([("eye", "f4", 3), ("U", "f4", 3), ("V", "f4", 3), ("W", "f4", 3), ("invTanHalf", "f4"), ("tanHalf", "f4"),
+                         ("aspect", "f4"), ("orthoHalfHeight", "f4"), ("mode", "u4"), ("width", "u4"), ("height", "u4")])
+
+
+def fill_camera(eye, U, V, W, fovY, width, height, *, ext=None, k3=False) -> np.ndarray:
+    """fill_camera into a one-element CAMERA_DTYPE array.  ``ext``: None (a null MrirtRenderExt) or (cameraMode, orthoHalfHeight)."""
+    l = lib()
+    assert l.probe_sizeof(0) == CAMERA_DTYPE.itemsize, (l.probe_sizeof(0), CAMERA_DTYPE.itemsize)
+    v = [np.ascontiguousarray(a, dtype=np.float32).reshape(3) for a in (eye, U, V, W)]
+    out = np.zeros(1, dtype=CAMERA_DTYPE)
+    mode, ohh = ext if ext is not None else (0, 0.0)
+    l.probe_fill_camera(*[_np_ptr(a) for a in v], float(np.float32(fovY)), int(width), int(height), int(ext is not None), int(mode),
+                        float(np.float32(ohh)), int(bool(k3)), _np_ptr(out))
+    return out
+
+
+def fill_k1args(params: np.ndarray) -> np.ndarray:
+    """params: (P, 14) float32 in K1_FIELDS order -> (P, sizeof(K1Args)) uint8, host memory."""
+    l = lib()
+    params = np.ascontiguousarray(params, dtype=np.float32).reshape(-1, len(K1_FIELDS))
+    out = np.zeros((params.shape[0], l.probe_sizeof(1)), dtype=np.uint8)
+    l.probe_fill_k1args(_np_ptr(params), params.shape[0], _np_ptr(out))
+    return out
+
+
+# ---- device entries (torch tensors on the GPU) ---------------------------------------------------------------------
+def _stream():
+    import torch
+    return torch.cuda.current_stream().cuda_stream
+
+
+def _dev(a, dtype=np.float32):
+    import torch
+    return torch.from_numpy(np.array(a, dtype=dtype, order="C", copy=True)).cuda()
+
+
+def _run(name, rc):
+    import torch
+    assert rc == 0, f"{name}: launch status {rc}"
+    torch.cuda.synchronize()
+
+
+def divu(x, d, *, strict=True, data=False):
+    """M<strict>::divu / divu_data of x[i] by make_udiv(d[i])."""
+    import torch
+    x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
+    d = np.ascontiguousarray(np.broadcast_to(np.asarray(d, dtype=np.float32), x.shape))
+    r, exact = make_udiv(d)
+    tx, td, tr, te = _dev(x), _dev(d), _dev(r), _dev(exact.view(np.int32), np.int32)
+    out = torch.empty_like(tx)
+    _run("probe_divu", lib().probe_divu(int(strict), int(data), tx.data_ptr(), td.data_ptr(), tr.data_ptr(), te.data_ptr(), out.data_ptr(),
+                                        x.size, _stream()))
+    return out.cpu().numpy()
+
+
+def exp(x, form):
+    import torch
+    tx = _dev(np.asarray(x, dtype=np.float32).reshape(-1))
+    out = torch.empty_like(tx)
+    _run("probe_exp", lib().probe_exp(int(form), tx.data_ptr(), out.data_ptr(), tx.numel(), _stream()))
+    return out.cpu().numpy()
+
+
+def pow_strict(x, y):
+    import torch
+    tx, ty = _dev(np.asarray(x, dtype=np.float32).reshape(-1)), _dev(np.asarray(y, dtype=np.float32).reshape(-1))
+    assert tx.numel() == ty.numel()
+    out = torch.empty_like(tx)
+    _run("probe_pow", lib().probe_pow(tx.data_ptr(), ty.data_ptr(), out.data_ptr(), tx.numel(), _stream()))
+    return out.cpu().numpy()
+
+
+def clampf(x, lo, hi):
+    import torch
+    tx, tl, th = (_dev(np.asarray(a, dtype=np.float32).reshape(-1)) for a in (x, lo, hi))
+    assert tx.numel() == tl.numel() == th.numel()
+    out = torch.empty_like(tx)
+    _run("probe_clampf", lib().probe_clampf(tx.data_ptr(), tl.data_ptr(), th.data_ptr(), out.data_ptr(), tx.numel(), _stream()))
+    return out.cpu().numpy()
+
+
+def clampf_k3(x):
+    """clampf(x, 0.01f, 0.25f): the literal bounds of the K3 march."""
+    import torch
+    tx = _dev(np.asarray(x, dtype=np.float32).reshape(-1))
+    out = torch.empty_like(tx)
+    _run("probe_clampf_k3", lib().probe_clampf_k3(tx.data_ptr(), out.data_ptr(), tx.numel(), _stream()))
+    return out.cpu().numpy()
+
+
+def satf(x):
+    import torch
+    tx = _dev(np.asarray(x, dtype=np.float32).reshape(-1))
+    out = torch.empty_like(tx)
+    _run("probe_satf", lib().probe_satf(tx.data_ptr(), out.data_ptr(), tx.numel(), _stream()))
+    return out.cpu().numpy()
+
+
+def lerp(a, b, t, *, strict):
+    import torch
+    ta, tb, tt = (_dev(np.asarray(v, dtype=np.float32).reshape(-1)) for v in (a, b, t))
+    assert ta.numel() == tb.numel() == tt.numel()
+    out = torch.empty_like(ta)
+    _run("probe_lerp", lib().probe_lerp(int(strict), ta.data_ptr(), tb.data_ptr(), tt.data_ptr(), out.data_ptr(), ta.numel(), _stream()))
+    return out.cpu().numpy()
+
+
+def lerp2(a, b, t, *, strict):
+    """a, b: (n, 2); t: (n,) -> (n, 2)."""
+    import torch
+    ta, tb, tt = (_dev(np.asarray(v, dtype=np.float32)) for v in (a, b, t))
+    n = tt.numel()
+    assert ta.shape == (n, 2) and tb.shape == (n, 2)
+    out = torch.empty_like(ta)
+    _run("probe_lerp2", lib().probe_lerp2(int(strict), ta.data_ptr(), tb.data_ptr(), tt.data_ptr(), out.data_ptr(), n, _stream()))
+    return out.cpu().numpy()
+
+
+def trilerp2(c, f, *, strict):
+    """c: (n, 8, 2) corners 000, 100, 010, 110, 001, 101, 011, 111; f: (n, 3) -> (n, 4): packed x, y, scalar x, y."""
+    import torch
+    tc, tf = _dev(np.asarray(c, dtype=np.float32)), _dev(np.asarray(f, dtype=np.float32))
+    n = tf.shape[0]
+    assert tc.shape == (n, 8, 2) and tf.shape == (n, 3)
+    out = torch.empty((n, 4), dtype=torch.float32, device="cuda")
+    _run("probe_trilerp2", lib().probe_trilerp2(int(strict), tc.data_ptr(), tf.data_ptr(), out.data_ptr(), n, _stream()))
+    return out.cpu().numpy()
+
+
+def primary_ray(cam: np.ndarray):
+    """cam: fill_camera's result -> ro, rd of shape (height, width, 3)."""
+    import torch
+    w, h = int(cam["width"][0]), int(cam["height"][0])
+    ro = torch.empty((h, w, 3), dtype=torch.float32, device="cuda")
+    rd = torch.empty_like(ro)
+    _run("probe_primary_ray", lib().probe_primary_ray(_np_ptr(cam), ro.data_ptr(), rd.data_ptr(), _stream()))
+    return ro.cpu().numpy(), rd.cpu().numpy()
+
+
+def store_rgba(rgba, *, half, offset=0, fill=0):
+    """Stores n texels at texel offset ``offset`` of a buffer of offset + n + 1 texels pre-filled with ``fill`` bytes; returns the
+    whole buffer as (offset + n + 1, 4) float16 / float32."""
+    import torch
+    t = _dev(np.asarray(rgba, dtype=np.float32))
+    n = t.shape[0]
+    assert t.shape == (n, 4)
+    out = torch.full((offset + n + 1, 4), 0, dtype=torch.float16 if half else torch.float32, device="cuda")
+    out.view(torch.uint8).fill_(fill)
+    _run("probe_store_rgba", lib().probe_store_rgba(int(half), t.data_ptr(), out.data_ptr(), offset, n, _stream()))
+    return out.cpu().numpy()
+
+
+def wave_count(v) -> int:
+    import torch
+    tv = _dev(np.asarray(v, dtype=np.uint32).view(np.int32), np.int32)
+    counter = torch.zeros(1, dtype=torch.int64, device="cuda")
+    _run("probe_wave_count", lib().probe_wave_count(tv.data_ptr(), counter.data_ptr(), tv.numel(), _stream()))
+    return int(counter.cpu().numpy().view(np.uint64)[0])
+
+
+def composite(combo, params, sel, v, g, rd, c0, t0):
+    """One compositing step per element.  params: (P, 14) K1_FIELDS; sel: (n,) block index -> (n, 4) C0 C1 C2 T, (n, 2) counters."""
+    import torch
+    blocks = fill_k1args(params)
+    sel = np.asarray(sel, dtype=np.int64)
+    assert sel.min() >= 0 and sel.max() < blocks.shape[0]
+    n = sel.size
+    ta = torch.from_numpy(blocks).cuda()
+    ts = _dev(sel.astype(np.int32), np.int32)
+    tv, tg, td, tc, tt = (_dev(np.asarray(a, dtype=np.float32)) for a in (v, g, rd, c0, t0))
+    assert tv.shape == (n,) and tg.shape == (n, 3) and td.shape == (n, 3) and tc.shape == (n,) and tt.shape == (n,)
+    out = torch.empty((n, 4), dtype=torch.float32, device="cuda")
+    cnt = torch.zeros((n, 2), dtype=torch.int32, device="cuda")
+    _run("probe_composite", lib().probe_composite(int(combo), ta.data_ptr(), ts.data_ptr(), tv.data_ptr(), tg.data_ptr(), td.data_ptr(),
+                                                  tc.data_ptr(), tt.data_ptr(), out.data_ptr(), cnt.data_ptr(), n, _stream()))
+    return out.cpu().numpy(), cnt.cpu().numpy()
+
+
+def fill_locate_args(params: np.ndarray) -> np.ndarray:
+    """params: (P, 9) float32: volMin[3], voxelSize[3], dims[3] -> (P, sizeof(K1Args)) uint8, host memory."""
+    l = lib()
+    params = np.ascontiguousarray(params, dtype=np.float32).reshape(-1, 9)
+    out = np.zeros((params.shape[0], l.probe_sizeof(1)), dtype=np.uint8)
+    l.probe_fill_locate_args(_np_ptr(params), params.shape[0], _np_ptr(out))
+    return out
+
+
+def locate(params, sel, ro, rd, t, *, strict=True):
+    """locate<strict> per element -> q (n, 3) float32, cell (n, 3) uint32, f (n, 3) float32."""
+    import torch
+    blocks = fill_locate_args(params)
+    sel = np.asarray(sel, dtype=np.int64)
+    assert sel.min() >= 0 and sel.max() < blocks.shape[0]
+    n = sel.size
+    ta = torch.from_numpy(blocks).cuda()
+    ts = _dev(sel.astype(np.int32), np.int32)
+    to, td, tt = (_dev(np.asarray(a, dtype=np.float32)) for a in (ro, rd, t))
+    assert to.shape == (n, 3) and td.shape == (n, 3) and tt.shape == (n,)
+    q = torch.empty((n, 3), dtype=torch.float32, device="cuda")
+    cell = torch.zeros((n, 3), dtype=torch.int32, device="cuda")
+    f = torch.empty_like(q)
+    _run("probe_locate", lib().probe_locate(int(strict), ta.data_ptr(), ts.data_ptr(), to.data_ptr(), td.data_ptr(), tt.data_ptr(),
+                                            q.data_ptr(), cell.data_ptr(), f.data_ptr(), n, _stream()))
+    return q.cpu().numpy(), cell.cpu().numpy().view(np.uint32), f.cpu().numpy()

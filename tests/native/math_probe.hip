@@ -1,0 +1,349 @@
+// TEST INFRASTRUCTURE: one entry point per device math primitive of csrc/mrirt_device.h / csrc/brats_device.h, so that
+// tests/test_gpu_math_primitives.py can run each function ON ITS OWN over chosen arguments and compare it with the exact
+// references of tests/math_ref.py.  Built by tests/math_probe.py into tests/native/_build/libmrirt_probe.so with the
+// product's own compiler flags (mrirt._lib.HIPCC_FLAGS: -O3 -ffp-contract=off are what the STRICT contract rests on); the
+// product's headers are included, nothing is copied from them, and none of this is part of libmrirt.so.
+//
+// Every device entry takes device pointers, a count and a stream, launches an element-wise grid-stride kernel of 256
+// threads and returns hipGetLastError().  The host entries (probe_make_udiv, probe_fill_exp_consts, probe_fill_camera,
+// probe_fill_k1args, probe_sizeof) run the product's host-side helpers and need no GPU.
+#include "../../mri-raytracer_amd/csrc/brats_device.h"
+
+namespace mrirt { thread_local int g_last_hip_error = 0; }      // declared by mrirt_host.h, defined in libmrirt.so only
+
+using namespace mrirt;
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int64_t kMaxBlocks = 4096;
+
+inline dim3 grid_for(int64_t n) {
+    int64_t b = (n + kThreads - 1) / kThreads;
+    if (b < 1) b = 1;
+    if (b > kMaxBlocks) b = kMaxBlocks;
+    return dim3((unsigned)b);
+}
+
+#define PROBE_LOOP(i, n) \
+    for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < (n); i += (int64_t)gridDim.x * kThreads)
+
+// ---- division ---------------------------------------------------------------------------------------------------
+template <bool STRICT, bool DATA>
+__global__ void __launch_bounds__(kThreads) divu_kernel(const float* __restrict__ x, const float* __restrict__ d,
+                                                        const float* __restrict__ r, const uint32_t* __restrict__ exact,
+                                                        float* __restrict__ out, int64_t n) {
+    PROBE_LOOP(i, n) {
+        UDiv u;
+        u.d = d[i]; u.r = r[i]; u.exact = exact[i];
+        out[i] = DATA ? M<STRICT>::divu_data(x[i], u) : M<STRICT>::divu(x[i], u);
+    }
+}
+
+// ---- exp: the four STRICT forms -------------------------------------------------------------------------------------
+template <int FORM>
+__global__ void __launch_bounds__(kThreads) exp_kernel(const float* __restrict__ x, float* __restrict__ out, int64_t n,
+                                                       ExpConsts ec) {
+    PROBE_LOOP(i, n) {
+        float y;
+        if constexpr (FORM == 0) y = M<true>::exp(x[i], ec);
+        else if constexpr (FORM == 1) y = M<true>::exp_lit(x[i]);
+        else if constexpr (FORM == 2) y = M<true>::exp_small(x[i], ec);
+        else y = M<true>::exp_small_lit(x[i]);
+        out[i] = y;
+    }
+}
+
+__global__ void __launch_bounds__(kThreads) pow_kernel(const float* __restrict__ x, const float* __restrict__ y,
+                                                       float* __restrict__ out, int64_t n) {
+    PROBE_LOOP(i, n) out[i] = M<true>::pow(x[i], y[i]);
+}
+
+__global__ void __launch_bounds__(kThreads) clamp_kernel(const float* __restrict__ x, const float* __restrict__ lo,
+                                                         const float* __restrict__ hi, float* __restrict__ out, int64_t n) {
+    PROBE_LOOP(i, n) out[i] = clampf(x[i], lo[i], hi[i]);
+}
+// ... and with the literal bounds of the K3 march's step clamp (volume_march.hip: clampf(d, 0.01f, 0.25f))
+__global__ void __launch_bounds__(kThreads) clamp_k3_kernel(const float* __restrict__ x, float* __restrict__ out, int64_t n) {
+    PROBE_LOOP(i, n) out[i] = clampf(x[i], 0.01f, 0.25f);
+}
+__global__ void __launch_bounds__(kThreads) sat_kernel(const float* __restrict__ x, float* __restrict__ out, int64_t n) {
+    PROBE_LOOP(i, n) out[i] = satf(x[i]);
+}
+
+// ---- lerp, lerp2, trilerp2 ------------------------------------------------------------------------------------------
+template <bool STRICT>
+__global__ void __launch_bounds__(kThreads) lerp_kernel(const float* __restrict__ a, const float* __restrict__ b,
+                                                        const float* __restrict__ t, float* __restrict__ out, int64_t n) {
+    PROBE_LOOP(i, n) out[i] = M<STRICT>::lerp(a[i], b[i], t[i]);
+}
+template <bool STRICT>
+__global__ void __launch_bounds__(kThreads) lerp2_kernel(const float* __restrict__ a, const float* __restrict__ b,
+                                                         const float* __restrict__ t, float* __restrict__ out, int64_t n) {
+    PROBE_LOOP(i, n) {
+        const f32x2 r = lerp2<STRICT>(f32x2{ a[2 * i], a[2 * i + 1] }, f32x2{ b[2 * i], b[2 * i + 1] }, t[i]);
+        out[2 * i] = r.x; out[2 * i + 1] = r.y;
+    }
+}
+// c: 16 floats per element (corner k of 000, 100, 010, 110, 001, 101, 011, 111 at c[2k], c[2k+1]); f: 3 per element;
+// out: 4 per element: the packed blend's two lanes, then the scalar trilerp<STRICT> of the same two lanes
+template <bool STRICT>
+__global__ void __launch_bounds__(kThreads) trilerp2_kernel(const float* __restrict__ c, const float* __restrict__ f,
+                                                            float* __restrict__ out, int64_t n) {
+    PROBE_LOOP(i, n) {
+        const float* q = c + 16 * i;
+        f32x2 k[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) k[j] = f32x2{ q[2 * j], q[2 * j + 1] };
+        const float fx = f[3 * i], fy = f[3 * i + 1], fz = f[3 * i + 2];
+        const f32x2 r = trilerp2<STRICT>(k[0], k[1], k[2], k[3], k[4], k[5], k[6], k[7], fx, fy, fz);
+        out[4 * i] = r.x; out[4 * i + 1] = r.y;
+        out[4 * i + 2] = trilerp<STRICT>(k[0].x, k[1].x, k[2].x, k[3].x, k[4].x, k[5].x, k[6].x, k[7].x, fx, fy, fz);
+        out[4 * i + 3] = trilerp<STRICT>(k[0].y, k[1].y, k[2].y, k[3].y, k[4].y, k[5].y, k[6].y, k[7].y, fx, fy, fz);
+    }
+}
+
+// ---- rays, stores, counters -----------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(kThreads) primary_ray_kernel(Camera cam, float* __restrict__ ro, float* __restrict__ rd, int64_t n) {
+    PROBE_LOOP(i, n) {
+        const uint32_t px = (uint32_t)(i % cam.width), py = (uint32_t)(i / cam.width);
+        float o[3], d[3];
+        primary_ray(cam, px, py, o, d);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { ro[3 * i + k] = o[k]; rd[3 * i + k] = d[k]; }
+    }
+}
+
+template <bool HALF>
+__global__ void __launch_bounds__(kThreads) store_rgba_kernel(const float* __restrict__ rgba, void* out, int64_t offset, int64_t n) {
+    PROBE_LOOP(i, n) store_rgba<HALF>(out, offset + i, rgba[4 * i], rgba[4 * i + 1], rgba[4 * i + 2], rgba[4 * i + 3]);
+}
+
+// one element per thread, whole waves: lanes past n add 0 (every lane of a wave takes part in the shuffle)
+__global__ void __launch_bounds__(kThreads) wave_count_kernel(const uint32_t* __restrict__ v, uint64_t* counter, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    wave_count_add(counter, i < n ? v[i] : 0u);
+}
+
+// ---- one compositing step on a fresh RayState -----------------------------------------------------------------------
+// args: the launch-constant blocks (probe_fill_k1args), sel[i] picks one; out: (C0, C1, C2, T) per element; cnt: (nLive,
+// nShaded) per element
+template <bool STRICT, bool SHADE, bool GAMMA1>
+__global__ void __launch_bounds__(kThreads) composite_kernel(const K1Args* __restrict__ args, const uint32_t* __restrict__ sel,
+                                                             const float* __restrict__ v, const float* __restrict__ g,
+                                                             const float* __restrict__ rd, const float* __restrict__ c0,
+                                                             const float* __restrict__ t0, float* __restrict__ out,
+                                                             uint32_t* __restrict__ cnt, int64_t n) {
+    PROBE_LOOP(i, n) {
+        const K1Args& a = args[sel[i]];
+        RayState r;
+        r.C0 = r.C1 = r.C2 = c0[i]; r.T = t0[i]; r.nLive = 0; r.nShaded = 0;
+        const float gg[3] = { g[3 * i], g[3 * i + 1], g[3 * i + 2] };
+        const float dd[3] = { rd[3 * i], rd[3 * i + 1], rd[3 * i + 2] };
+        Labels lb; lb.seg = 0; lb.pred = 0;
+        composite<STRICT, SHADE, GAMMA1, false>(a, dd, lb, v[i], gg, r);
+        out[4 * i] = r.C0; out[4 * i + 1] = r.C1; out[4 * i + 2] = r.C2; out[4 * i + 3] = r.T;
+        cnt[2 * i] = r.nLive; cnt[2 * i + 1] = r.nShaded;
+    }
+}
+
+// ---- one sample's cell: o + t d, the voxel-size quotient, sampleLinear's clamp / floor / fract -------------------------
+// args: blocks of probe_fill_locate_args, sel[i] picks one; ro, rd, q, f: 3 floats per element; cell: 3 words
+template <bool STRICT>
+__global__ void __launch_bounds__(kThreads) locate_kernel(const K1Args* __restrict__ args, const uint32_t* __restrict__ sel,
+                                                          const float* __restrict__ ro, const float* __restrict__ rd,
+                                                          const float* __restrict__ t, float* __restrict__ q, uint32_t* __restrict__ cell,
+                                                          float* __restrict__ f, int64_t n) {
+    PROBE_LOOP(i, n) {
+        const float o[3] = { ro[3 * i], ro[3 * i + 1], ro[3 * i + 2] };
+        const float d[3] = { rd[3 * i], rd[3 * i + 1], rd[3 * i + 2] };
+        Cell c;
+        locate<STRICT>(args[sel[i]], o, d, t[i], c);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) q[3 * i + k] = c.q[k];
+        cell[3 * i] = c.ix; cell[3 * i + 1] = c.iy; cell[3 * i + 2] = c.iz;
+        f[3 * i] = c.fx; f[3 * i + 1] = c.fy; f[3 * i + 2] = c.fz;
+    }
+}
+
+inline int launched() { return (int)hipGetLastError(); }
+
+}  // namespace
+
+extern "C" {
+
+// ---- host entries (no GPU) ------------------------------------------------------------------------------------------
+void probe_make_udiv(const float* d, float* r, uint32_t* exact, int64_t n) {
+    for (int64_t i = 0; i < n; ++i) { const UDiv u = make_udiv(d[i]); r[i] = u.r; exact[i] = u.exact; }
+}
+// out: log2e, ln2hi, ln2lo, c[0..12]
+void probe_fill_exp_consts(double* out) {
+    ExpConsts e;
+    fill_exp_consts(e);
+    out[0] = e.log2e; out[1] = e.ln2hi; out[2] = e.ln2lo;
+    for (int i = 0; i < 13; ++i) out[3 + i] = e.c[i];
+}
+// hasExt == 0 passes ext = nullptr (perspective)
+void probe_fill_camera(const float* eye, const float* U, const float* V, const float* W, float fovY, uint32_t width, uint32_t height,
+                       int hasExt, uint32_t cameraMode, float orthoHalfHeight, int k3Aspect, Camera* out) {
+    MrirtRenderExt ext;
+    memset(&ext, 0, sizeof ext);
+    ext.cameraMode = cameraMode;
+    ext.orthoHalfHeight = orthoHalfHeight;
+    memset(out, 0, sizeof *out);
+    fill_camera(*out, eye, U, V, W, fovY, width, height, hasExt ? &ext : nullptr, k3Aspect != 0);
+}
+uint32_t probe_sizeof(int which) { return which == 0 ? (uint32_t)sizeof(Camera) : which == 1 ? (uint32_t)sizeof(K1Args) : (uint32_t)sizeof(UDiv); }
+// The launch constants composite() reads, made the way the host makes them (make_udiv, fill_exp_consts; tfLo and expSmall
+// as brats_march.hip's prepare() writes them).  p: 14 floats per block: ww, wl, gamma, wSum, intensityAlpha, stepSize, ka,
+// kd, ks, gradEps, specPow2, halfInvVoxel[3].  out: count blocks of probe_sizeof(1) bytes (host memory).
+void probe_fill_k1args(const float* p, int64_t count, void* out) {
+    K1Args* a = static_cast<K1Args*>(out);
+    for (int64_t i = 0; i < count; ++i, p += 14) {
+        memset(&a[i], 0, sizeof(K1Args));
+        a[i].wwDiv = make_udiv(p[0]);
+        a[i].tfLo = p[1] - p[0] * 0.5f;
+        a[i].gamma = p[2];
+        a[i].wsum = make_udiv(p[3]);
+        a[i].intensityAlpha = p[4];
+        a[i].stepSize = p[5];
+        a[i].ka = p[6]; a[i].kd = p[7]; a[i].ks = p[8]; a[i].gradEps = p[9];
+        a[i].specPow2 = (uint32_t)p[10];
+        for (int k = 0; k < 3; ++k) a[i].halfInvVoxel[k] = p[11 + k];
+        fill_exp_consts(a[i].ec);
+        a[i].expSmall = (fabsf(p[4] * p[5]) <= 0.125f) ? 1u : 0u;
+    }
+}
+
+// The launch constants locate() reads, as brats_march.hip's prepare() writes them.  p: 9 floats per block: volMin[3],
+// voxelSize[3], dims[3].  out: count blocks of probe_sizeof(1) bytes (host memory).
+void probe_fill_locate_args(const float* p, int64_t count, void* out) {
+    K1Args* a = static_cast<K1Args*>(out);
+    for (int64_t i = 0; i < count; ++i, p += 9) {
+        memset(&a[i], 0, sizeof(K1Args));
+        for (int k = 0; k < 3; ++k) {
+            a[i].bmin[k] = p[k];
+            a[i].vox[k] = make_udiv(p[3 + k]);
+            a[i].hiLin[k] = (float)(uint32_t)p[6 + k] - 1.001f;
+        }
+    }
+}
+
+// ---- device entries -------------------------------------------------------------------------------------------------
+int probe_divu(int strict, int data, const float* x, const float* d, const float* r, const uint32_t* exact, float* out, int64_t n,
+               hipStream_t s) {
+    if (n <= 0) return 0;
+    const dim3 g = grid_for(n);
+    if (strict && data) divu_kernel<true, true><<<g, kThreads, 0, s>>>(x, d, r, exact, out, n);
+    else if (strict) divu_kernel<true, false><<<g, kThreads, 0, s>>>(x, d, r, exact, out, n);
+    else if (data) divu_kernel<false, true><<<g, kThreads, 0, s>>>(x, d, r, exact, out, n);
+    else divu_kernel<false, false><<<g, kThreads, 0, s>>>(x, d, r, exact, out, n);
+    return launched();
+}
+// form 0: exp(x, consts); 1: exp_lit; 2: exp_small(x, consts); 3: exp_small_lit
+int probe_exp(int form, const float* x, float* out, int64_t n, hipStream_t s) {
+    if (n <= 0) return 0;
+    if (form < 0 || form > 3) return -1;
+    ExpConsts ec;
+    fill_exp_consts(ec);
+    const dim3 g = grid_for(n);
+    if (form == 0) exp_kernel<0><<<g, kThreads, 0, s>>>(x, out, n, ec);
+    else if (form == 1) exp_kernel<1><<<g, kThreads, 0, s>>>(x, out, n, ec);
+    else if (form == 2) exp_kernel<2><<<g, kThreads, 0, s>>>(x, out, n, ec);
+    else exp_kernel<3><<<g, kThreads, 0, s>>>(x, out, n, ec);
+    return launched();
+}
+int probe_pow(const float* x, const float* y, float* out, int64_t n, hipStream_t s) {
+    if (n <= 0) return 0;
+    pow_kernel<<<grid_for(n), kThreads, 0, s>>>(x, y, out, n);
+    return launched();
+}
+int probe_clampf(const float* x, const float* lo, const float* hi, float* out, int64_t n, hipStream_t s) {
+    if (n <= 0) return 0;
+    clamp_kernel<<<grid_for(n), kThreads, 0, s>>>(x, lo, hi, out, n);
+    return launched();
+}
+int probe_clampf_k3(const float* x, float* out, int64_t n, hipStream_t s) {
+    if (n <= 0) return 0;
+    clamp_k3_kernel<<<grid_for(n), kThreads, 0, s>>>(x, out, n);
+    return launched();
+}
+int probe_satf(const float* x, float* out, int64_t n, hipStream_t s) {
+    if (n <= 0) return 0;
+    sat_kernel<<<grid_for(n), kThreads, 0, s>>>(x, out, n);
+    return launched();
+}
+int probe_lerp(int strict, const float* a, const float* b, const float* t, float* out, int64_t n, hipStream_t s) {
+    if (n <= 0) return 0;
+    if (strict) lerp_kernel<true><<<grid_for(n), kThreads, 0, s>>>(a, b, t, out, n);
+    else lerp_kernel<false><<<grid_for(n), kThreads, 0, s>>>(a, b, t, out, n);
+    return launched();
+}
+// a, b, out: 2 floats per element; t: 1
+int probe_lerp2(int strict, const float* a, const float* b, const float* t, float* out, int64_t n, hipStream_t s) {
+    if (n <= 0) return 0;
+    if (strict) lerp2_kernel<true><<<grid_for(n), kThreads, 0, s>>>(a, b, t, out, n);
+    else lerp2_kernel<false><<<grid_for(n), kThreads, 0, s>>>(a, b, t, out, n);
+    return launched();
+}
+int probe_trilerp2(int strict, const float* c, const float* f, float* out, int64_t n, hipStream_t s) {
+    if (n <= 0) return 0;
+    if (strict) trilerp2_kernel<true><<<grid_for(n), kThreads, 0, s>>>(c, f, out, n);
+    else trilerp2_kernel<false><<<grid_for(n), kThreads, 0, s>>>(c, f, out, n);
+    return launched();
+}
+// cam: HOST pointer (probe_fill_camera's output); ro, rd: 3 floats per pixel, width * height pixels, row-major
+int probe_primary_ray(const Camera* cam, float* ro, float* rd, hipStream_t s) {
+    const int64_t n = (int64_t)cam->width * cam->height;
+    if (n <= 0) return 0;
+    primary_ray_kernel<<<grid_for(n), kThreads, 0, s>>>(*cam, ro, rd, n);
+    return launched();
+}
+// out holds offset + n texels (8 bytes each when half, else 16); texel offset + i receives rgba[4 i .. 4 i + 3]
+int probe_store_rgba(int half, const float* rgba, void* out, int64_t offset, int64_t n, hipStream_t s) {
+    if (n <= 0) return 0;
+    if (offset < 0) return -1;
+    if (half) store_rgba_kernel<true><<<grid_for(n), kThreads, 0, s>>>(rgba, out, offset, n);
+    else store_rgba_kernel<false><<<grid_for(n), kThreads, 0, s>>>(rgba, out, offset, n);
+    return launched();
+}
+int probe_wave_count(const uint32_t* v, uint64_t* counter, int64_t n, hipStream_t s) {
+    if (n <= 0) return 0;
+    const int64_t blocks = (n + kThreads - 1) / kThreads;
+    if (blocks > (int64_t)1 << 24) return -1;
+    wave_count_kernel<<<dim3((unsigned)blocks), kThreads, 0, s>>>(v, counter, n);
+    return launched();
+}
+// args: DEVICE copy of probe_fill_locate_args' blocks; every sel[i] must index one of them
+int probe_locate(int strict, const void* args, const uint32_t* sel, const float* ro, const float* rd, const float* t, float* q,
+                 uint32_t* cell, float* f, int64_t n, hipStream_t s) {
+    if (n <= 0) return 0;
+    const K1Args* a = static_cast<const K1Args*>(args);
+    if (strict) locate_kernel<true><<<grid_for(n), kThreads, 0, s>>>(a, sel, ro, rd, t, q, cell, f, n);
+    else locate_kernel<false><<<grid_for(n), kThreads, 0, s>>>(a, sel, ro, rd, t, q, cell, f, n);
+    return launched();
+}
+// combo: bit 0 STRICT, bit 1 SHADE, bit 2 GAMMA1 (LABELS = false).  args: DEVICE copy of probe_fill_k1args' blocks; every
+// sel[i] must index one of them.  v, c0, t0: 1 float per element; g, rd: 3; out: 4; cnt: 2 words.
+int probe_composite(int combo, const void* args, const uint32_t* sel, const float* v, const float* g, const float* rd,
+                    const float* c0, const float* t0, float* out, uint32_t* cnt, int64_t n, hipStream_t s) {
+    if (n <= 0) return 0;
+    if (combo < 0 || combo > 7) return -1;
+    const K1Args* a = static_cast<const K1Args*>(args);
+    const dim3 gr = grid_for(n);
+#define PROBE_COMPOSITE(ST, SH, G1) composite_kernel<ST, SH, G1><<<gr, kThreads, 0, s>>>(a, sel, v, g, rd, c0, t0, out, cnt, n)
+    switch (combo) {
+        case 0: PROBE_COMPOSITE(false, false, false); break;
+        case 1: PROBE_COMPOSITE(true, false, false); break;
+        case 2: PROBE_COMPOSITE(false, true, false); break;
+        case 3: PROBE_COMPOSITE(true, true, false); break;
+        case 4: PROBE_COMPOSITE(false, false, true); break;
+        case 5: PROBE_COMPOSITE(true, false, true); break;
+        case 6: PROBE_COMPOSITE(false, true, true); break;
+        default: PROBE_COMPOSITE(true, true, true); break;
+    }
+#undef PROBE_COMPOSITE
+    return launched();
+}
+
+}  // extern "C"
