@@ -540,7 +540,8 @@ def _split_grads(gw: torch.Tensor, gb: torch.Tensor, dims: Sequence[int]):
 def make_loss_and_grad(num_classes: int, class_weights, dice_weight: float, fourier_freqs: int):
     """inr/inr/model.py:64-90 on the GPU: returns ``f(params, coords, intensities, labels) -> ((loss, aux), grads)`` with the
     reference's return shape — ``loss`` a 0-d device tensor, ``aux = {"ce_per_class", "dice_per_class"}`` (device, (C,)),
-    ``grads`` a list of ``{"W", "b"}`` device tensors shaped like ``params`` (NumPy arrays or device tensors).  One fp32
+    ``grads`` a list of ``{"W", "b"}`` device tensors shaped like ``params`` (NumPy arrays or device tensors);
+    ``intensities`` may be None for a network without modalities.  One fp32
     forward, the loss and one backward pass (csrc/inr_train.hip); nothing synchronises with the host."""
     cw = [float(v) for v in np.asarray(class_weights, dtype=np.float32).reshape(-1)]
     if len(cw) != int(num_classes):
@@ -553,10 +554,10 @@ def make_loss_and_grad(num_classes: int, class_weights, dice_weight: float, four
         dims = _param_dims(Ws, bs)
         if dims[-1] != int(num_classes):
             raise ValueError(f"the network has {dims[-1]} outputs for {num_classes} classes")
-        c, f = _dev_f32(coords, dev), _dev_f32(intensities, dev)
+        c, f = _dev_f32(coords, dev), (_dev_f32(intensities, dev) if intensities is not None else None)
         n = int(c.shape[0])
         lab = torch.as_tensor(labels).to(dev).to(torch.int32).contiguous()
-        desc = train_desc(dims, fourier_freqs, f.shape[1] if f.dim() == 2 else 0)
+        desc = train_desc(dims, fourier_freqs, f.shape[1] if f is not None and f.dim() == 2 else 0)
         w_flat, b_flat = torch.cat([W.reshape(-1) for W in Ws]), torch.cat(bs)
         scratch = train_scratch(desc, n, dev)
         logits = forward_f32(desc, w_flat, b_flat, c, f, n, scratch)

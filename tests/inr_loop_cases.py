@@ -82,9 +82,12 @@ TRAJ_TOL = dict(params=1.71e-6, losses=8.99e-7)
 TRAJ_NEAR_KINK = 0.0        # fraction of the last micro-batch's points near the kink in the fp64 run (bar: 0.02)
 
 
-def run_cfg(accum):
+RUN_LONG_MICRO = 16385      # the first micro-batch with 512-point slabs (33 of them, the last of one point)
+
+
+def run_cfg(accum, micro=None):
     """The configuration of the run tests: clipping active (the raw norm is above it at the start), warm-up then cosine."""
-    return dict(K=RUN_NET["K"], classes=RUN_NET["classes"], micro=RUN_NET["micro"], accum=accum, seed=RUN_SEED, cw=RUN_CW, dw=RUN_DW,
+    return dict(K=RUN_NET["K"], classes=RUN_NET["classes"], micro=micro or RUN_NET["micro"], accum=accum, seed=RUN_SEED, cw=RUN_CW, dw=RUN_DW,
                 peak=5e-3, end=1e-4, warmup=2, decay_steps=12, clip=0.25)
 
 

@@ -3,7 +3,8 @@
   sampler      coords, feats, labels EQUAL the restatement, for every cache / batch size / batch index / seed of inr_loop_cases.py
   adamw        integer gradients: the norm is exact and p, mu, nu EQUAL the float32 restatement; float gradients: the norm within
                the derived bound, the update bit for bit given the device's clip factor; inf poisons, it does not fault
-  run          mrirt_inr_train_run EQUALS the composition of the separate calls, and a run continued at first_step = 3
+  run          mrirt_inr_train_run EQUALS the composition of the separate calls (micro-batch 300, and 16385 with its 512-point
+               slabs), and a run continued at first_step = 3
   trajectory   8 steps against the fp64 CPU loop on the same batches, within the tolerance measured from fp32 on the CPU
   train_inr    40 steps end to end, checkpoint / resume bit for bit, the loss falls
   operators    torch.ops.mrirt.* and torch.ops.mrirt_native.* give the ctypes path's bits
@@ -191,6 +192,22 @@ def test_run_equals_composition(inr, caches, accum):
     assert _same(hist6[:3], hist) and _same(hist6[3:], more)
     for what, x, y in zip(("w", "b", "mu_w", "mu_b", "nu_w", "nu_b"), _bits(b), _bits(whole)):
         assert _same(x, y), what
+
+
+def test_run_equals_composition_at_long_slabs(inr, caches):
+    """The assertion of test_run_equals_composition at a micro-batch that takes 512-point slabs: 16385 points, accum 2, two
+    optimiser steps."""
+    cache, c = caches["run"], cases.run_cfg(2, micro=cases.RUN_LONG_MICRO)
+    assert c["micro"] == 16385
+    desc, dims = _desc(inr)
+    a, b = inr.AdamWState.from_params(cases.run_layers()), inr.AdamWState.from_params(cases.run_layers())
+    want_hist = _composition(inr, cache, desc, c, a, 2)
+    hist = _np(inr.train_run(desc, cache, _cfg(inr, c), b, 2))
+    assert a.step == b.step == 2 and hist.shape == (2, 2, 1 + 2 * c["classes"])
+    assert _same(hist, want_hist) and np.isfinite(hist).all()
+    for what, x, y in zip(("w", "b", "mu_w", "mu_b", "nu_w", "nu_b"), _bits(b), _bits(a)):
+        assert _same(x, y), what
+    assert not _same(_bits(b)[0], ref.flat(cases.run_layers())[0])
 
 
 def test_trajectory_against_fp64(inr, caches):

@@ -30,11 +30,27 @@ def _flat(layers, dev):
     return w, b
 
 
-@pytest.mark.parametrize("i", range(len(cases.EXACT)), ids=[cases.exact_id(c) for c in cases.EXACT])
-def test_integer_nets_are_exact(inr, i):
-    c = cases.exact_case(i)
+def _want_grads(c, w_scale=1):
+    """The int64 gradients of a case in the flat layouts, the initial values of an accumulate case added."""
     ref = c["ref"]
-    assert ref["bound"] < 2 ** 24
+    want_w = np.concatenate([g[0].reshape(-1) for g in ref["grads"]])
+    want_b = np.concatenate([g[1].reshape(-1) for g in ref["grads"]])
+    if c.get("init_w") is not None:
+        want_w = want_w + w_scale * c["init_w"].astype(np.int64)
+        want_b = want_b + c["init_b"].astype(np.int64)
+    return want_w, want_b
+
+
+def _assert_grads(gw, gb, want_w, want_b):
+    assert np.array_equal(gw, gw.round()) and np.array_equal(gb, gb.round())
+    bad = np.flatnonzero(gw.astype(np.int64) != want_w)
+    assert bad.size == 0, (bad[:8], gw[bad[:8]], want_w[bad[:8]])
+    bad = np.flatnonzero(gb.astype(np.int64) != want_b)
+    assert bad.size == 0, (bad[:8], gb[bad[:8]], want_b[bad[:8]])
+
+
+def _exact_step(inr, c):
+    """One forward + backward of an exact case through mrirt.inr: (logits, gw, gb) as NumPy arrays."""
     dev = torch.device("cuda:0")
     n = c["x"].shape[0]
     desc = inr.train_desc(c["dims"])
@@ -42,22 +58,107 @@ def test_integer_nets_are_exact(inr, i):
     scratch = inr.train_scratch(desc, n, dev)
     x = torch.from_numpy(c["x"]).to(dev)
     logits = inr.forward_f32(desc, w, b, None, x, n, scratch)
-    assert np.array_equal(logits.cpu().numpy().astype(np.int64), ref["logits"])
     acc = c["init_w"] is not None
     gw0 = torch.from_numpy(c["init_w"]).to(dev) if acc else None
     gb0 = torch.from_numpy(c["init_b"]).to(dev) if acc else None
     gw, gb = inr.backward_f32(desc, w, n, torch.from_numpy(c["dlogits"]).to(dev), scratch, gw0, gb0, accumulate=acc)
-    gw, gb = gw.cpu().numpy(), gb.cpu().numpy()
-    want_w = np.concatenate([g[0].reshape(-1) for g in ref["grads"]])
-    want_b = np.concatenate([g[1].reshape(-1) for g in ref["grads"]])
-    if acc:
-        want_w = want_w + c["init_w"].astype(np.int64)
-        want_b = want_b + c["init_b"].astype(np.int64)
-    assert np.array_equal(gw, gw.round()) and np.array_equal(gb, gb.round())
-    bad = np.flatnonzero(gw.astype(np.int64) != want_w)
-    assert bad.size == 0, (bad[:8], gw[bad[:8]], want_w[bad[:8]])
-    bad = np.flatnonzero(gb.astype(np.int64) != want_b)
-    assert bad.size == 0, (bad[:8], gb[bad[:8]], want_b[bad[:8]])
+    return logits.cpu().numpy(), gw.cpu().numpy(), gb.cpu().numpy()
+
+
+def _assert_exact_step(inr, c):
+    ref = c["ref"]
+    assert ref["bound"] < 2 ** 24
+    logits, gw, gb = _exact_step(inr, c)
+    bad = np.argwhere(logits.astype(np.int64) != ref["logits"])
+    assert bad.size == 0 and np.array_equal(logits, logits.round()), (len(bad), bad[:4])
+    _assert_grads(gw, gb, *_want_grads(c))
+    return logits, gw, gb
+
+
+@pytest.mark.parametrize("i", range(len(cases.EXACT)), ids=[cases.exact_id(c) for c in cases.EXACT])
+def test_integer_nets_are_exact(inr, i):
+    _assert_exact_step(inr, cases.exact_case(i))
+
+
+@pytest.mark.parametrize("i", range(len(cases.SWEEP)), ids=[cases.exact_id(c) for c in cases.SWEEP])
+def test_shape_sweep_is_exact(inr, i):
+    """Every (hidden, in), (hidden, layers), (hidden, out) pair of the sweep's axes at n = 321 (inr_train_cases._sweep_nets)."""
+    _assert_exact_step(inr, cases.sweep_case(i))
+
+
+@pytest.mark.parametrize("i", range(len(cases.BATCH)), ids=[cases.exact_id(c) for c in cases.BATCH])
+def test_batch_sweep_is_exact(inr, i):
+    """Both sides of every doubling of the slab length from 256 to 4096; one case runs twice and demands the same bytes."""
+    c = cases.batch_case(i)
+    first = _assert_exact_step(inr, c)
+    if cases.BATCH[i] == cases.BATCH_REPEAT:
+        for a, b in zip(first, _exact_step(inr, c)):
+            assert a.tobytes() == b.tobytes()
+
+
+@pytest.mark.parametrize("n", cases.GUARD_NS)
+def test_scratch_exactly_as_long_as_the_abi_asks(inr, n):
+    """The step through the raw C ABI with a scratch of exactly mrirt_inr_train_scratch_bytes(desc, n) bytes between two
+    guard blocks: n = 16384 has the most slabs of any batch size, at 16385 the count drops (and the slab length doubles),
+    65537 is the first n of the loss kernel's stride loop.  mrirt_inr_loss runs on the same scratch between the two passes,
+    as the one-call loop uses it; the gradients are those of the batch sweep."""
+    import ctypes as C
+    import mrirt
+    lib = mrirt._lib.lib()
+    c = cases.batch_case(cases.batch_index(7, n))
+    assert c["x"].shape[0] == n
+    dev = torch.device("cuda:0")
+    desc = inr.train_desc(c["dims"])
+    nbytes = int(lib.mrirt_inr_train_scratch_bytes(C.byref(desc), n))
+    assert nbytes > 0 and nbytes >= int(lib.mrirt_inr_loss_scratch_bytes(n))
+    guard = 4096
+    buf = torch.full((guard + nbytes + guard,), 0x5A, dtype=torch.uint8, device=dev)
+    scratch = C.c_void_p(buf.data_ptr() + guard)
+    assert scratch.value % 16 == 0
+    w, b = _flat(c["layers"], dev)
+    x, dl = torch.from_numpy(c["x"]).to(dev), torch.from_numpy(c["dlogits"]).to(dev)
+    out = c["dims"][-1]
+    logits = torch.full((n + 1, out), -7.0, dtype=torch.float32, device=dev)
+    acc = c["init_w"] is not None
+    gw = torch.from_numpy(c["init_w"]).to(dev) if acc else torch.full_like(w, -7.0)
+    gb = torch.from_numpy(c["init_b"]).to(dev) if acc else torch.full_like(b, -7.0)
+    labels = torch.from_numpy((np.arange(n) % out).astype(np.int32)).to(dev)
+    loss, aux, dl2 = (torch.full(s, -7.0, dtype=torch.float32, device=dev) for s in ((2,), (2 * out + 1,), (n + 1, out)))
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    p = lambda t: C.c_void_p(t.data_ptr())
+    assert lib.mrirt_inr_forward_f32(C.byref(desc), p(w), p(b), None, p(x), n, p(logits), scratch, nbytes, stream) == 0
+    assert lib.mrirt_inr_loss(p(logits), p(labels), n, out, (C.c_float * out)(*([1.0] * out)), 0.5, p(loss), p(aux), p(dl2), scratch, nbytes,
+                              stream) == 0
+    assert lib.mrirt_inr_backward(C.byref(desc), p(w), n, p(dl), p(gw), p(gb), 1 if acc else 0, scratch, nbytes, stream) == 0
+    torch.cuda.synchronize()
+    assert bool((buf[:guard] == 0x5A).all()), "the guard below the scratch was overwritten"
+    assert bool((buf[guard + nbytes:] == 0x5A).all()), "the guard above the scratch was overwritten"
+    assert bool((logits[n] == -7.0).all()) and bool((dl2[n] == -7.0).all()) and float(loss[1]) == -7.0 and float(aux[2 * out]) == -7.0
+    assert bool(torch.isfinite(loss[0])) and bool(torch.isfinite(aux[:2 * out]).all()) and bool(torch.isfinite(dl2[:n]).all())
+    assert np.array_equal(logits[:n].cpu().numpy().astype(np.int64), c["ref"]["logits"])
+    _assert_grads(gw.cpu().numpy(), gb.cpu().numpy(), *_want_grads(c))
+    # one byte less is refused before anything is launched
+    assert lib.mrirt_inr_backward(C.byref(desc), p(w), n, p(dl), p(gw), p(gb), 0, scratch, nbytes - 1, stream) == -5
+
+
+@pytest.mark.parametrize("i", range(len(cases.FEATURE0)), ids=[cases.feature0_id(c) for c in cases.FEATURE0])
+def test_feature_builder_without_a_sine_is_exact(inr, i):
+    """KIND_FOURIER_RELU with K = 0: x = (coords, modalities) assembled by tr_features_kernel, feats=None without modalities.
+    Every value is a multiple of 1/2: 2 x logits, 2 x dW and db EQUAL the int64 step of the doubled net."""
+    c = cases.feature0_case(i)
+    ref = c["ref"]
+    assert ref["bound"] < 2 ** 24
+    dev = torch.device("cuda:0")
+    n = c["coords"].shape[0]
+    desc = inr.train_desc(c["dims"], 0, c["M"])
+    w, b = _flat(c["layers"], dev)
+    scratch = inr.train_scratch(desc, n, dev)
+    feats = None if c["feats"] is None else torch.from_numpy(c["feats"]).to(dev)
+    logits = inr.forward_f32(desc, w, b, torch.from_numpy(c["coords"]).to(dev), feats, n, scratch).cpu().numpy()
+    assert np.array_equal(2.0 * logits.astype(np.float64), ref["logits"].astype(np.float64))
+    gw, gb = inr.backward_f32(desc, w, n, torch.from_numpy(c["dlogits"]).to(dev), scratch)
+    want_w, want_b = _want_grads(c)
+    _assert_grads(2.0 * gw.cpu().numpy().astype(np.float64), gb.cpu().numpy(), want_w, want_b)
 
 
 def _figure(found, what, err, tol):
@@ -82,6 +183,10 @@ def test_loss_kernel_alone(inr, i):
     _figure(found, "loss", abs(float(loss) - ref["loss"]) / max(abs(ref["loss"]), 1e-300), cases.tol(tol["loss"]))
     _figure(found, "aux", cases.rel_max(aux.cpu().numpy(), ref["aux"]), cases.tol(tol["aux"]))
     _figure(found, "dlogits", cases.rel_max(dl.cpu().numpy(), ref["dlogits"]), cases.tol(tol["dlogits"]))
+    first = cases.LOSS_FIRST_STRIDED
+    if c["logits"].shape[0] > first:                     # the points past 256 blocks x 256 threads, on the scale of all rows
+        err = np.abs(dl[first:].cpu().numpy().astype(np.float64) - ref["dlogits"][first:]).max() / np.abs(ref["dlogits"]).max()
+        _figure(found, f"dlogits, rows {first}..", float(err), cases.tol(tol["dlogits"]))
     _hold(found)
 
 
@@ -121,9 +226,11 @@ def test_make_loss_and_grad_matches_fp64(inr, name):
     # logits and dlogits of the same step through the entry points that make_loss_and_grad calls
     dev = loss.device
     w, b = _flat(c["layers"], dev)
-    desc = inr.train_desc(c["dims"], c["K"], c["feats"].shape[1])
+    desc = inr.train_desc(c["dims"], c["K"], c["M"])
     scratch = inr.train_scratch(desc, c["n"], dev)
-    logits = inr.forward_f32(desc, w, b, torch.from_numpy(c["coords"]).to(dev), torch.from_numpy(c["feats"]).to(dev), c["n"], scratch)
+    feats = None if c["feats"] is None else torch.from_numpy(c["feats"]).to(dev)          # None: the case without modalities
+    assert (feats is None) == (c["M"] == 0)
+    logits = inr.forward_f32(desc, w, b, torch.from_numpy(c["coords"]).to(dev), feats, c["n"], scratch)
     loss2, _, dl = inr.loss_and_dlogits(logits, torch.from_numpy(c["labels"]).to(dev), cases.CLASS_WEIGHTS, cases.DICE_WEIGHT)
     assert torch.equal(loss2.reshape(()), loss)
     found = []

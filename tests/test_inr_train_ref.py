@@ -70,6 +70,61 @@ def test_exact_cases_are_exact_in_fp32(i):
         assert np.array_equal(gw, rw) and np.array_equal(gb, rb)
 
 
+def _check_exact(c, autograd=True):
+    r = c["ref"]
+    assert r["bound"] < 2 ** 24
+    assert r["dead_units"] >= 1 and r["zero_units"] >= 1
+    if c["init_w"] is not None:
+        assert np.abs(c["init_w"]).max() + r["bound"] < 2 ** 24
+    if autograd:
+        got = tr.step(c["layers"], c["x"], lambda lg: ((lg * torch.as_tensor(c["dlogits"], dtype=lg.dtype)).sum(), None))
+        assert np.array_equal(got["logits"], r["logits"])
+        for (gw, gb), (rw, rb) in zip(got["grads"], r["grads"]):
+            assert np.array_equal(gw, rw) and np.array_equal(gb, rb)
+
+
+@pytest.mark.parametrize("i", range(len(cases.SWEEP)), ids=[cases.exact_id(c) for c in cases.SWEEP])
+def test_sweep_cases_are_exact_in_fp32(i):
+    _check_exact(cases.sweep_case(i))
+
+
+@pytest.mark.parametrize("i", range(len(cases.BATCH)), ids=[cases.exact_id(c) for c in cases.BATCH])
+def test_batch_cases_are_exact_in_fp32(i):
+    _check_exact(cases.batch_case(i))
+
+
+@pytest.mark.parametrize("i", range(len(cases.FEATURE0)), ids=[cases.feature0_id(c) for c in cases.FEATURE0])
+def test_feature0_cases_are_exact_in_fp32(i):
+    """The doubled net's int64 step is 2 x logits, 2 x dW and 1 x db of the network on (coords, modalities): checked against
+    fp64 autograd of the network itself; below 2^24 on the doubled net, every value of the step is exact in fp32."""
+    c = cases.feature0_case(i)
+    r = c["ref"]
+    assert r["bound"] < 2 ** 24 and r["dead_units"] >= 1 and r["zero_units"] >= 1
+    assert np.array_equal(c["x"], tr.build_input(c["coords"], c["feats"], 0, torch.float64).numpy())
+    assert set(np.unique(c["coords"])) == {-1.0, -0.5, 0.0, 0.5, 1.0} and (c["feats"] is None) == (c["M"] == 0)
+    got = tr.step(c["layers"], c["x"], lambda lg: ((lg * torch.as_tensor(c["dlogits"], dtype=lg.dtype)).sum(), None))
+    assert np.array_equal(2 * got["logits"], r["logits"])
+    for (gw, gb), (rw, rb) in zip(got["grads"], r["grads"]):
+        assert np.array_equal(2 * gw, rw) and np.array_equal(gb, rb)
+    assert any((np.abs(gw) % 1 == 0.5).any() for gw, _ in got["grads"])          # the halves do occur: the scaling is needed
+
+
+def test_sweep_and_batch_cases_cover_the_issue():
+    S, B = cases.SWEEP, cases.BATCH
+    assert len(S) == 36 and len({cases.exact_id(c) for c in S + B + cases.EXACT}) == len(S) + len(B) + len(cases.EXACT)
+    hids = {32, 64, 128, 256}
+    for axis, values in ((0, cases.SWEEP_INS), (2, cases.SWEEP_DEPTHS), (3, cases.SWEEP_OUTS)):
+        assert {(c[1], c[axis]) for c in S} == {(h, v) for h in hids for v in values}, axis
+    assert cases.SWEEP_INS == (1, 15, 16, 17, 63, 64, 65, 127, 128) and cases.SWEEP_DEPTHS == (2, 3, 8)
+    assert cases.SWEEP_OUTS == (1, 2, 3, 5, 15, 16)
+    assert {c[4] for c in S} == {321} and sum(c[5] for c in S) == 9
+    assert [c[4] for c in B if c[:4] == (7, 32, 2, 4)] == [16383, 16384, 16385, 32768, 32769, 65536, 65537, 131073]
+    assert [c[4] for c in B if c[:4] == (31, 64, 3, 4)] == [16383, 16384, 16385, 32768, 32769] and len(B) == 13
+    assert [c for c in B if c[5]] == [(7, 32, 2, 4, 65537, True)] and cases.BATCH_REPEAT in B
+    assert all((7, 32, 2, 4, n, n == 65537) in B for n in cases.GUARD_NS) and cases.GUARD_NS == (16384, 16385, 65537)
+    assert {c[0] for c in cases.FEATURE0} == {0, 5, 8}
+
+
 def test_exact_cases_cover_the_shapes():
     E = cases.EXACT
     assert {c[1] for c in E} == {32, 64, 128, 256} and {c[2] for c in E} == {2, 3, 5, 8}
@@ -109,5 +164,6 @@ def test_loss_cases(i):
 
 def test_loss_cases_cover_the_issue():
     L = cases.LOSS
-    assert {c[0] for c in L} == {1, 5, 1000} and {c[1] for c in L} == {1, 4, 16} and {c[2] for c in L} == {0.0, 0.5, 1.0}
+    assert {c[0] for c in L} == {1, 5, 1000, 100003} and {c[1] for c in L} == {1, 4, 16} and {c[2] for c in L} == {0.0, 0.5, 1.0}
     assert max(c[3] for c in L) == 80.0
+    assert {c[1:3] for c in L if c[0] == 100003} == {(4, 0.5), (16, 0.5)}          # beyond the cap of 256 loss blocks

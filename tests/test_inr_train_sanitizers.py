@@ -47,6 +47,7 @@ def test_index_arithmetic_under_asan_and_ubsan():
     shapes = [(ind, hid, depth, out, n, 1) for ind, hid, depth, out, n, _ in cases.EXACT]
     shapes += [(3 + 6 * K + M, hid, nh + 1, nc, n, 0) for K, M, hid, nh, nc, n in cases.E2E.values()]
     shapes += [(31, 64, 5, 4, 4096, 0), (7, 32, 2, 1, 16385, 0)]          # the timing tool's small shape; the first n with longer slabs
+    shapes += [(ind, hid, depth, out, n, 0) for ind, hid, depth, out, n, _ in cases.BATCH if ind == 7]     # every slab length up to 4096
     args = [str(v) for s in shapes for v in s]
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
     r = subprocess.run([str(exe), *args], capture_output=True, text=True, env=env, timeout=600)
