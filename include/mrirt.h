@@ -34,7 +34,9 @@ extern "C" {
  *    mrirt_render_brats_backward (the K1 backward pass on LINEAR grids; no new struct);
  *    the INR training loop: MrirtInrCache, MrirtAdamW, MrirtInrTrainCfg, MrirtInrTrainState (mrirt_sizeof(7..10)),
  *    mrirt_inr_sample_batch, mrirt_inr_adamw_scratch_bytes, mrirt_inr_adamw_step, mrirt_inr_lr_schedule,
- *    mrirt_inr_train_run_scratch_bytes, mrirt_inr_train_run. */
+ *    mrirt_inr_train_run_scratch_bytes, mrirt_inr_train_run;
+ *    SIREN training (no new struct): mrirt_siren_train_scratch_bytes, mrirt_siren_forward_f32, mrirt_siren_backward,
+ *    mrirt_siren_train_run_scratch_bytes, mrirt_siren_train_run. */
 #define MRIRT_ABI_VERSION 4
 
 typedef enum MrirtStatus {
@@ -520,6 +522,33 @@ int64_t mrirt_inr_train_run_scratch_bytes(const MrirtInrDesc* desc, const MrirtI
 int mrirt_inr_train_run(const MrirtInrDesc* desc, const MrirtInrCache* cache, const MrirtInrTrainCfg* cfg,
                         const MrirtInrTrainState* state, uint64_t first_step, uint32_t steps, float* history, void* scratch,
                         int64_t scratch_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------ */
+/* SIREN training (notebooks/neumors_inr.ipynb:1150-1200): the fp32 step and loop for     */
+/* the sine kinds.  Added within ABI 4: new symbols only                                  */
+/* ------------------------------------------------------------------------------------ */
+/* The twins of mrirt_inr_train_scratch_bytes / _forward_f32 / _backward / _train_run_scratch_bytes / _train_run for
+ * MRIRT_INR_SIREN (x = (coords, modalities), inDim = 3 + numMods) and MRIRT_INR_RAW_SIREN (x = feats[n][inDim]) with
+ * fourierFreqs == 0 and a finite w0 != 0; every other kind is MRIRT_ERR_ARG (the ReLU kinds train through mrirt_inr_*, which
+ * go on refusing the SIREN kinds: one way to train each kind).  Same layouts of w_f32 / b_f32 / gradients, same argument
+ * meaning, same checks before any launch, no host synchronisation, no allocation, flags bit 0 = accumulate.
+ *   forward   x' = w0 x (one fp32 multiply);  a_l = (in_l . W_l) + b_l with in_0 = x', in_l = h_{l-1};  h_l = sin32(a_l);
+ *             the head is linear.  c_l = cos32(a_l) is stored in scratch beside h_l.
+ *   backward  da_l = dh_l c_l (one fp32 multiply);  dh_{l-1} = da_l W_l^T;  dW_l = in_l^T da_l;  db_l = sum_p da_l
+ * sin32 / cos32: the fp32 argument widened to fp64, reduced by multiples of pi/2, evaluated by polynomials in fp64 and
+ * rounded once to fp32 — correctly rounded on every argument tested for |a| <= 2^20 (the stated domain); a finite argument
+ * beyond it gives sin = +-0, cos = 1; NaN and +-inf give NaN.  mrirt_inr_loss, mrirt_inr_sample_batch, mrirt_inr_adamw_step
+ * and mrirt_inr_lr_schedule serve both families.  mrirt_siren_train_run: desc is MRIRT_INR_SIREN with
+ * numMods == cache->numMods; it enqueues the same sequence as mrirt_inr_train_run with the mrirt_siren_* step. */
+int64_t mrirt_siren_train_scratch_bytes(const MrirtInrDesc* desc, int64_t n);
+int mrirt_siren_forward_f32(const MrirtInrDesc* desc, const float* w_f32, const float* b_f32, const float* coords,
+                            const float* feats, int64_t n, float* logits, void* scratch, int64_t scratch_bytes, void* stream);
+int mrirt_siren_backward(const MrirtInrDesc* desc, const float* w_f32, int64_t n, const float* dlogits, float* grad_w,
+                         float* grad_b, uint32_t flags, void* scratch, int64_t scratch_bytes, void* stream);
+int64_t mrirt_siren_train_run_scratch_bytes(const MrirtInrDesc* desc, const MrirtInrCache* cache, const MrirtInrTrainCfg* cfg);
+int mrirt_siren_train_run(const MrirtInrDesc* desc, const MrirtInrCache* cache, const MrirtInrTrainCfg* cfg,
+                          const MrirtInrTrainState* state, uint64_t first_step, uint32_t steps, float* history, void* scratch,
+                          int64_t scratch_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------ */
 /* Exact distance transform and Hausdorff distance (inr/inr/model.py:164-195)            */

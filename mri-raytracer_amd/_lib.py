@@ -35,6 +35,8 @@ ABI_SYMBOLS = [
     "mrirt_inr_train_scratch_bytes", "mrirt_inr_loss_scratch_bytes", "mrirt_inr_forward_f32", "mrirt_inr_loss", "mrirt_inr_backward",
     "mrirt_inr_sample_batch", "mrirt_inr_adamw_scratch_bytes", "mrirt_inr_adamw_step", "mrirt_inr_lr_schedule",
     "mrirt_inr_train_run_scratch_bytes", "mrirt_inr_train_run",
+    "mrirt_siren_train_scratch_bytes", "mrirt_siren_forward_f32", "mrirt_siren_backward",
+    "mrirt_siren_train_run_scratch_bytes", "mrirt_siren_train_run",
 ]
 
 ABI_VERSION = 4          # MRIRT_ABI_VERSION of include/mrirt.h this binding was written against
@@ -369,6 +371,9 @@ def lib() -> C.CDLL:
     l.mrirt_inr_train_run.argtypes = [C.POINTER(InrDesc), C.POINTER(InrCache), C.POINTER(InrTrainCfg), C.POINTER(InrTrainState), u64, u32,
                                       vp, vp, i64, vp]
     l.mrirt_inr_train_run.restype = i32
+    for twin in ("train_scratch_bytes", "forward_f32", "backward", "train_run_scratch_bytes", "train_run"):     # the SIREN twins
+        src, dst = getattr(l, "mrirt_inr_" + twin), getattr(l, "mrirt_siren_" + twin)
+        dst.argtypes, dst.restype = src.argtypes, src.restype
     l.mrirt_status_string.argtypes = [i32]
     l.mrirt_status_string.restype = C.c_char_p
     l.mrirt_sizeof.argtypes = [u32]

@@ -152,13 +152,14 @@ static int check_opt_scratch(const void* scratch, int64_t have, uint64_t need) {
 static bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
 // the shapes, the cache and the configuration of a run; fills the layouts
-static int check_run(const MrirtInrDesc* desc, const MrirtInrCache* cache, const MrirtInrTrainCfg* cfg, TrainLayout& L, RunLayout& R) {
+static int check_run(const MrirtInrDesc* desc, bool siren, const MrirtInrCache* cache, const MrirtInrTrainCfg* cfg, TrainLayout& L, RunLayout& R) {
     if (!desc || !cache || !cfg) return MRIRT_ERR_NULL;
     int rc = check_cache(cache);
     if (rc != MRIRT_OK) return rc;
-    if (desc->kind != MRIRT_INR_FOURIER_RELU || desc->numMods != cache->numMods) return MRIRT_ERR_ARG;
+    if (desc->kind != (siren ? MRIRT_INR_SIREN : MRIRT_INR_FOURIER_RELU) || desc->numMods != cache->numMods) return MRIRT_ERR_ARG;
     if (cfg->microBatch < 1 || cfg->microBatch >= (1ll << 31) || cfg->accum < 1) return MRIRT_ERR_ARG;
-    if (mrirt_inr_train_scratch_bytes(desc, cfg->microBatch) <= 0) return MRIRT_ERR_ARG;
+    const int64_t stepBytes = siren ? mrirt_siren_train_scratch_bytes(desc, cfg->microBatch) : mrirt_inr_train_scratch_bytes(desc, cfg->microBatch);
+    if (stepBytes <= 0) return MRIRT_ERR_ARG;
     if (desc->outDim < 1 || desc->outDim > kLossMaxClasses || !isfinite(cfg->diceWeight)) return MRIRT_ERR_ARG;
     for (uint32_t k = 0; k < desc->outDim; ++k)
         if (!isfinite(cfg->classWeights[k])) return MRIRT_ERR_ARG;
@@ -166,6 +167,7 @@ static int check_run(const MrirtInrDesc* desc, const MrirtInrCache* cache, const
     double lr;
     if ((rc = mrirt_inr_lr_schedule(cfg->peakLr, cfg->minLr, cfg->warmupSteps, cfg->decaySteps, 0, &lr)) != MRIRT_OK) return rc;
     L = train_layout(desc->numLayers, desc->inDim, desc->hidden, desc->outDim, cfg->microBatch);
+    L.bytes = (uint64_t)stepBytes;                       // the SIREN step's scratch carries the cosines behind the ReLU step's
     R = run_layout(L, cfg->microBatch, cache->numMods);
     return MRIRT_OK;
 }
@@ -242,20 +244,28 @@ extern "C" int mrirt_inr_lr_schedule(double peak, double end, uint32_t warmup, u
     return MRIRT_OK;
 }
 
-extern "C" int64_t mrirt_inr_train_run_scratch_bytes(const MrirtInrDesc* desc, const MrirtInrCache* cache, const MrirtInrTrainCfg* cfg) {
+static int64_t run_scratch_bytes(const MrirtInrDesc* desc, bool siren, const MrirtInrCache* cache, const MrirtInrTrainCfg* cfg) {
     TrainLayout L;
     RunLayout R;
-    return check_run(desc, cache, cfg, L, R) == MRIRT_OK ? (int64_t)R.bytes : 0;
+    return check_run(desc, siren, cache, cfg, L, R) == MRIRT_OK ? (int64_t)R.bytes : 0;
 }
 
-extern "C" int mrirt_inr_train_run(const MrirtInrDesc* desc, const MrirtInrCache* cache, const MrirtInrTrainCfg* cfg,
-                                   const MrirtInrTrainState* state, uint64_t first_step, uint32_t steps, float* history,
-                                   void* scratch, int64_t scratch_bytes, void* stream) {
+extern "C" int64_t mrirt_inr_train_run_scratch_bytes(const MrirtInrDesc* desc, const MrirtInrCache* cache, const MrirtInrTrainCfg* cfg) {
+    return run_scratch_bytes(desc, false, cache, cfg);
+}
+extern "C" int64_t mrirt_siren_train_run_scratch_bytes(const MrirtInrDesc* desc, const MrirtInrCache* cache, const MrirtInrTrainCfg* cfg) {
+    return run_scratch_bytes(desc, true, cache, cfg);
+}
+
+// One loop for both families: the kind picks the public forward / backward pair, everything else is shared.
+static int train_run(const MrirtInrDesc* desc, bool siren, const MrirtInrCache* cache, const MrirtInrTrainCfg* cfg,
+                     const MrirtInrTrainState* state, uint64_t first_step, uint32_t steps, float* history,
+                     void* scratch, int64_t scratch_bytes, void* stream) {
     TrainLayout L;
     RunLayout R;
     if (!desc || !cache || !cfg || !state || !history) return MRIRT_ERR_NULL;
     if (!state->w || !state->b || !state->mu_w || !state->mu_b || !state->nu_w || !state->nu_b) return MRIRT_ERR_NULL;
-    int rc = check_run(desc, cache, cfg, L, R);
+    int rc = check_run(desc, siren, cache, cfg, L, R);
     if (rc != MRIRT_OK) return rc;
     if (steps < 1) return MRIRT_ERR_ARG;
     if ((rc = check_opt_scratch(scratch, scratch_bytes, R.bytes)) != MRIRT_OK) return rc;
@@ -277,10 +287,10 @@ extern "C" int mrirt_inr_train_run(const MrirtInrDesc* desc, const MrirtInrCache
         for (uint32_t a = 0; a < cfg->accum; ++a) {
             float* h = history + ((uint64_t)k * cfg->accum + a) * (1u + 2u * C);
             if ((rc = mrirt_inr_sample_batch(cache, cfg->seed, t * cfg->accum + a, n, coords, feats, labels, stream)) != MRIRT_OK) return rc;
-            if ((rc = mrirt_inr_forward_f32(desc, state->w, state->b, coords, feats, n, logits, base, (int64_t)R.stepBytes, stream)) != MRIRT_OK) return rc;
+            if ((rc = (siren ? mrirt_siren_forward_f32 : mrirt_inr_forward_f32)(desc, state->w, state->b, coords, feats, n, logits, base, (int64_t)R.stepBytes, stream)) != MRIRT_OK) return rc;
             if ((rc = mrirt_inr_loss(logits, labels, n, C, cfg->classWeights, cfg->diceWeight, h, h + 1, dlogits, base,
                                      (int64_t)R.stepBytes, stream)) != MRIRT_OK) return rc;
-            if ((rc = mrirt_inr_backward(desc, state->w, n, dlogits, gw, gb, a ? 1u : 0u, base, (int64_t)R.stepBytes, stream)) != MRIRT_OK) return rc;
+            if ((rc = (siren ? mrirt_siren_backward : mrirt_inr_backward)(desc, state->w, n, dlogits, gw, gb, a ? 1u : 0u, base, (int64_t)R.stepBytes, stream)) != MRIRT_OK) return rc;
         }
         double lr;
         if ((rc = mrirt_inr_lr_schedule(cfg->peakLr, cfg->minLr, cfg->warmupSteps, cfg->decaySteps, t, &lr)) != MRIRT_OK) return rc;
@@ -289,4 +299,16 @@ extern "C" int mrirt_inr_train_run(const MrirtInrDesc* desc, const MrirtInrCache
                                        (int64_t)R.nb, &hp, t, gscale, gnorm, base + R.offOpt, (int64_t)R.optBytes, stream)) != MRIRT_OK) return rc;
     }
     return MRIRT_OK;
+}
+
+extern "C" int mrirt_inr_train_run(const MrirtInrDesc* desc, const MrirtInrCache* cache, const MrirtInrTrainCfg* cfg,
+                                   const MrirtInrTrainState* state, uint64_t first_step, uint32_t steps, float* history,
+                                   void* scratch, int64_t scratch_bytes, void* stream) {
+    return train_run(desc, false, cache, cfg, state, first_step, steps, history, scratch, scratch_bytes, stream);
+}
+
+extern "C" int mrirt_siren_train_run(const MrirtInrDesc* desc, const MrirtInrCache* cache, const MrirtInrTrainCfg* cfg,
+                                     const MrirtInrTrainState* state, uint64_t first_step, uint32_t steps, float* history,
+                                     void* scratch, int64_t scratch_bytes, void* stream) {
+    return train_run(desc, true, cache, cfg, state, first_step, steps, history, scratch, scratch_bytes, stream);
 }

@@ -120,6 +120,8 @@ struct TrGemmArgs {
     const float* bias;           // bias form
     uint32_t relu;
     const float* mask;           // mask form: the saved activation of the layer below, [M][ldc]; gradient passes where it is > 0
+                                 // cosine-scale form (SIREN): the saved cosine of the layer below, [M][ldc]; C = v * mask
+    float* cosOut;               // sine form (SIREN): cos of the pre-activation, [M][ldc] beside C = sin
 };
 
 // Scratch offset of layer l's input: x for layer 0, else the saved h_{l-1} (which the forward of layer l - 1 writes)
@@ -165,6 +167,44 @@ MRIRT_HD TrGemmArgs tr_mask_args(const TrainLayout& L, uint32_t l, int64_t n, co
 // Element i of a reduced slab ((in + 1) x out): rows < in are dW, row in is db
 MRIRT_HD float* tr_reduce_dst(uint32_t i, uint32_t in, uint32_t out, float* gw, float* gb) {
     return i < in * out ? gw + i : gb + (i - in * out);
+}
+
+// ---- SIREN ---------------------------------------------------------------------------------------------
+// The step's scratch is the ReLU step's with one more region behind it: c_0 .. c_{L-2}, the cosines of the hidden
+// pre-activations (n x hidden each), which the forward's sine epilogue stores beside h_l and the backward multiplies by.
+struct SirenLayout {
+    TrainLayout T;               // T.bytes: where the cosines start
+    uint64_t offC, bytes;
+};
+MRIRT_HD SirenLayout siren_layout(uint32_t numLayers, uint32_t inDim, uint32_t hidden, uint32_t outDim, int64_t n) {
+    SirenLayout S;
+    S.T = train_layout(numLayers, inDim, hidden, outDim, n);
+    S.offC = S.T.bytes;
+    S.bytes = S.offC + (uint64_t)(numLayers - 1) * train_act_bytes(S.T, n);
+    return S;
+}
+// Scratch offset of c_l, the cosine of hidden layer l's pre-activation (l < numLayers - 1)
+MRIRT_HD uint64_t tr_cos_offset(const SirenLayout& S, uint32_t l, int64_t n) { return S.offC + (uint64_t)l * train_act_bytes(S.T, n); }
+// H . W + b, then sin into C and cos into cosOut (hidden layers; the head is tr_forward_args, which is linear there)
+MRIRT_HD TrGemmArgs tr_sine_args(const SirenLayout& S, uint32_t l, int64_t n, const float* h, const float* w, const float* b, float* C,
+                                 float* cosOut) {
+    TrGemmArgs a = tr_forward_args(S.T, l, n, h, w, b, C);
+    a.relu = 0u;
+    a.cosOut = cosOut;
+    return a;
+}
+// dZ . W^T, times the cosine of the layer below (c_{l-1})
+MRIRT_HD TrGemmArgs tr_cos_args(const SirenLayout& S, uint32_t l, int64_t n, const float* dz, const float* w, const float* cosPrev,
+                                float* dzPrev) {
+    return tr_mask_args(S.T, l, n, dz, w, cosPrev, dzPrev);
+}
+// Element i of x'[n][inDim] = w0 * x: where x comes from.  src 0: coords[off], 1: feats[off]
+MRIRT_HD void tr_siren_feature_src(int64_t i, uint32_t inDim, uint32_t M, uint32_t raw, uint32_t& src, int64_t& off) {
+    const int64_t p = i / inDim;
+    const uint32_t f = (uint32_t)(i - p * inDim);
+    if (raw) { src = 1; off = i; }
+    else if (f < 3) { src = 0; off = 3 * p + f; }
+    else { src = 1; off = p * M + (f - 3); }
 }
 
 // LDS image of a staged tile: [k][non] with a row pitch that spreads one MFMA operand read (4 k x 16 non) over 64 banks

@@ -9,14 +9,19 @@
 //   backward  per layer: H^T . dZ over split-n slabs (db as the row of ones) -> fixed-order slab sum; dZ . W^T, masked
 // The three products are one LDS-tiled GEMM template; its index arithmetic lives in inr_train.h.  No float atomics: every sum
 // over the batch has a fixed order, so two runs on the same inputs give the same bits.
+//
+// SIREN kinds run the same pipeline through entry points of their own (mrirt_siren_*): the inputs are
+// scaled by w0, the hidden layers' epilogue takes the STRICT sine of siren_sincos.h and saves the cosine beside it, and the
+// backward multiplies by that cosine where the ReLU step masks.
 #include "inr_train.h"
+#include "siren_sincos.h"
 #include "mrirt_host.h"
 
 namespace mrirt {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-enum { kEpiBias = 0, kEpiMask = 1, kEpiSlab = 2 };
+enum { kEpiBias = 0, kEpiMask = 1, kEpiSlab = 2, kEpiSine = 3, kEpiCos = 4 };
 
 template <int R, bool KFAST>
 __device__ __forceinline__ void tr_fetch(const TrView& v, uint32_t non0, int64_t k0, int64_t kEnd, float (&reg)[R / 16]) {
@@ -91,8 +96,17 @@ __global__ __launch_bounds__(kTrThreads) void tr_gemm_kernel(TrGemmArgs a) {
             } else if (EPI == kEpiMask) {
                 const int64_t at = (int64_t)row * a.ldc + col;
                 a.C[at] = a.mask[at] > 0.0f ? v : 0.0f;
-            } else {
+            } else if (EPI == kEpiSlab) {
                 a.C[(uint64_t)blockIdx.z * a.slabStride + (uint64_t)row * a.N + col] = v;
+            } else if (EPI == kEpiSine) {                // one accumulator register at a time: the fp64 sincos keeps few live values
+                const int64_t at = (int64_t)row * a.ldc + col;
+                float sn, cs;
+                siren_sincos(v + a.bias[col], sn, cs);
+                a.C[at] = sn;
+                a.cosOut[at] = cs;
+            } else {
+                const int64_t at = (int64_t)row * a.ldc + col;
+                a.C[at] = v * a.mask[at];
             }
         }
     }
@@ -140,6 +154,17 @@ __global__ __launch_bounds__(256) void tr_features_kernel(const float* coords, c
         v = __builtin_amdgcn_sinf(__builtin_fmaf(coords[3 * p + axis], mult, isSin ? 0.0f : 0.25f));
     } else v = feats[p * M + (f - 3 - 6 * K)];
     x[i] = v;
+}
+
+// SIREN: x'[n][inDim] = w0 * (coords, modalities), or w0 * feats for the raw kind; one fp32 multiply per element
+__global__ __launch_bounds__(256) void tr_siren_features_kernel(const float* coords, const float* feats, int64_t n, uint32_t inDim,
+                                                                uint32_t M, uint32_t raw, float w0, float* x) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n * (int64_t)inDim) return;
+    uint32_t src;
+    int64_t off;
+    tr_siren_feature_src(i, inDim, M, raw, src, off);
+    x[i] = w0 * (src ? feats[off] : coords[off]);
 }
 
 // ---- loss ----------------------------------------------------------------------------------------------------------------------
@@ -287,12 +312,19 @@ __global__ __launch_bounds__(kLossThreads) void loss_grad_kernel(LossArgs a) {
 
 // ---- host ----------------------------------------------------------------------------------------------------------------------
 
-static int train_desc(const MrirtInrDesc* d, int64_t n, TrainLayout& L) {
+// The shapes one family of entry points takes: the ReLU kinds for mrirt_inr_*, the SIREN kinds (no Fourier features, a
+// finite non-zero w0) for mrirt_siren_*.  L.bytes is the family's scratch size.
+static int train_desc(const MrirtInrDesc* d, int64_t n, bool siren, TrainLayout& L, SirenLayout& S) {
     if (!d) return MRIRT_ERR_NULL;
-    if (d->kind != MRIRT_INR_FOURIER_RELU && d->kind != MRIRT_INR_RAW_RELU) return MRIRT_ERR_ARG;
+    if (siren) {
+        if (d->kind != MRIRT_INR_SIREN && d->kind != MRIRT_INR_RAW_SIREN) return MRIRT_ERR_ARG;
+        if (d->fourierFreqs != 0 || !isfinite(d->w0) || d->w0 == 0.0f) return MRIRT_ERR_ARG;
+    } else if (d->kind != MRIRT_INR_FOURIER_RELU && d->kind != MRIRT_INR_RAW_RELU) return MRIRT_ERR_ARG;
     if (mrirt_inr_pack_bytes(d) <= 0) return MRIRT_ERR_ARG;             // the shapes the packer accepts
     if (n < 1 || n >= (1ll << 31)) return MRIRT_ERR_ARG;
-    L = train_layout(d->numLayers, d->inDim, d->hidden, d->outDim, n);
+    S = siren_layout(d->numLayers, d->inDim, d->hidden, d->outDim, n);
+    L = S.T;
+    if (siren) L.bytes = S.bytes;
     return MRIRT_OK;
 }
 
@@ -306,39 +338,64 @@ static int check_scratch(const void* scratch, int64_t have, uint64_t need) {
 
 using namespace mrirt;
 
-extern "C" int64_t mrirt_inr_train_scratch_bytes(const MrirtInrDesc* desc, int64_t n) {
+static int64_t scratch_bytes_of(const MrirtInrDesc* desc, int64_t n, bool siren) {
     TrainLayout L;
-    return train_desc(desc, n, L) == MRIRT_OK ? (int64_t)L.bytes : 0;
+    SirenLayout S;
+    return train_desc(desc, n, siren, L, S) == MRIRT_OK ? (int64_t)L.bytes : 0;
 }
+
+extern "C" int64_t mrirt_inr_train_scratch_bytes(const MrirtInrDesc* desc, int64_t n) { return scratch_bytes_of(desc, n, false); }
+extern "C" int64_t mrirt_siren_train_scratch_bytes(const MrirtInrDesc* desc, int64_t n) { return scratch_bytes_of(desc, n, true); }
 
 extern "C" int64_t mrirt_inr_loss_scratch_bytes(int64_t n) {
     return (n < 1 || n >= (1ll << 31)) ? 0 : (int64_t)loss_scratch_bytes(n);
 }
 
-extern "C" int mrirt_inr_forward_f32(const MrirtInrDesc* desc, const float* w_f32, const float* b_f32, const float* coords,
-                                     const float* feats, int64_t n, float* logits, void* scratch, int64_t scratch_bytes,
-                                     void* stream) {
+static int forward_f32(const MrirtInrDesc* desc, bool siren, const float* w_f32, const float* b_f32, const float* coords,
+                       const float* feats, int64_t n, float* logits, void* scratch, int64_t scratch_bytes, void* stream) {
     TrainLayout L;
+    SirenLayout S;
     if (!desc || !w_f32 || !b_f32 || !logits) return MRIRT_ERR_NULL;
-    int rc = train_desc(desc, n, L);
+    int rc = train_desc(desc, n, siren, L, S);
     if (rc != MRIRT_OK) return rc;
-    const bool raw = desc->kind == MRIRT_INR_RAW_RELU;
+    const bool raw = desc->kind == MRIRT_INR_RAW_RELU || desc->kind == MRIRT_INR_RAW_SIREN;
     if ((!raw && !coords) || ((raw || desc->numMods > 0) && !feats)) return MRIRT_ERR_NULL;
     if ((rc = check_scratch(scratch, scratch_bytes, L.bytes)) != MRIRT_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     char* base = (char*)scratch;
     float* x = (float*)(base + L.offX);
     const int64_t total = n * (int64_t)L.inDim;
-    hipLaunchKernelGGL(tr_features_kernel, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, s, coords, feats, n, L.inDim,
-                       desc->fourierFreqs, desc->numMods, raw ? 1u : 0u, x);
+    if (siren)
+        hipLaunchKernelGGL(tr_siren_features_kernel, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, s, coords, feats, n, L.inDim,
+                           desc->numMods, raw ? 1u : 0u, desc->w0, x);
+    else
+        hipLaunchKernelGGL(tr_features_kernel, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, s, coords, feats, n, L.inDim,
+                           desc->fourierFreqs, desc->numMods, raw ? 1u : 0u, x);
     MRIRT_HIP(hipGetLastError());
     const float* h = x;
     for (uint32_t l = 0; l < L.numLayers; ++l) {
-        float* out = l + 1 == L.numLayers ? logits : (float*)(base + tr_in_offset(L, l + 1, n));
-        if ((rc = launch_gemm<true, false, kEpiBias>(tr_forward_args(L, l, n, h, w_f32, b_f32, out), 1, s)) != MRIRT_OK) return rc;
+        const bool head = l + 1 == L.numLayers;
+        float* out = head ? logits : (float*)(base + tr_in_offset(L, l + 1, n));
+        if (siren && !head)
+            rc = launch_gemm<true, false, kEpiSine>(tr_sine_args(S, l, n, h, w_f32, b_f32, out, (float*)(base + tr_cos_offset(S, l, n))), 1, s);
+        else
+            rc = launch_gemm<true, false, kEpiBias>(tr_forward_args(L, l, n, h, w_f32, b_f32, out), 1, s);
+        if (rc != MRIRT_OK) return rc;
         h = out;
     }
     return MRIRT_OK;
+}
+
+extern "C" int mrirt_inr_forward_f32(const MrirtInrDesc* desc, const float* w_f32, const float* b_f32, const float* coords,
+                                     const float* feats, int64_t n, float* logits, void* scratch, int64_t scratch_bytes,
+                                     void* stream) {
+    return forward_f32(desc, false, w_f32, b_f32, coords, feats, n, logits, scratch, scratch_bytes, stream);
+}
+
+extern "C" int mrirt_siren_forward_f32(const MrirtInrDesc* desc, const float* w_f32, const float* b_f32, const float* coords,
+                                       const float* feats, int64_t n, float* logits, void* scratch, int64_t scratch_bytes,
+                                       void* stream) {
+    return forward_f32(desc, true, w_f32, b_f32, coords, feats, n, logits, scratch, scratch_bytes, stream);
 }
 
 extern "C" int mrirt_inr_loss(const float* logits, const int32_t* labels, int64_t n, uint32_t num_classes,
@@ -365,11 +422,12 @@ extern "C" int mrirt_inr_loss(const float* logits, const int32_t* labels, int64_
     return MRIRT_OK;
 }
 
-extern "C" int mrirt_inr_backward(const MrirtInrDesc* desc, const float* w_f32, int64_t n, const float* dlogits, float* grad_w,
-                                  float* grad_b, uint32_t flags, void* scratch, int64_t scratch_bytes, void* stream) {
+static int backward_f32(const MrirtInrDesc* desc, bool siren, const float* w_f32, int64_t n, const float* dlogits, float* grad_w,
+                        float* grad_b, uint32_t flags, void* scratch, int64_t scratch_bytes, void* stream) {
     TrainLayout L;
+    SirenLayout S;
     if (!desc || !w_f32 || !dlogits || !grad_w || !grad_b) return MRIRT_ERR_NULL;
-    int rc = train_desc(desc, n, L);
+    int rc = train_desc(desc, n, siren, L, S);
     if (rc != MRIRT_OK) return rc;
     if (flags > 1u) return MRIRT_ERR_ARG;
     if ((rc = check_scratch(scratch, scratch_bytes, L.bytes)) != MRIRT_OK) return rc;
@@ -386,8 +444,22 @@ extern "C" int mrirt_inr_backward(const MrirtInrDesc* desc, const float* w_f32, 
         MRIRT_HIP(hipGetLastError());
         if (l == 0) break;
         float* dzPrev = (float*)(base + tr_dz_offset(L, l, n));
-        if ((rc = launch_gemm<true, true, kEpiMask>(tr_mask_args(L, l, n, dz, w_f32, hin, dzPrev), 1, s)) != MRIRT_OK) return rc;
+        if (siren)
+            rc = launch_gemm<true, true, kEpiCos>(tr_cos_args(S, l, n, dz, w_f32, (const float*)(base + tr_cos_offset(S, l - 1, n)), dzPrev), 1, s);
+        else
+            rc = launch_gemm<true, true, kEpiMask>(tr_mask_args(L, l, n, dz, w_f32, hin, dzPrev), 1, s);
+        if (rc != MRIRT_OK) return rc;
         dz = dzPrev;
     }
     return MRIRT_OK;
+}
+
+extern "C" int mrirt_inr_backward(const MrirtInrDesc* desc, const float* w_f32, int64_t n, const float* dlogits, float* grad_w,
+                                  float* grad_b, uint32_t flags, void* scratch, int64_t scratch_bytes, void* stream) {
+    return backward_f32(desc, false, w_f32, n, dlogits, grad_w, grad_b, flags, scratch, scratch_bytes, stream);
+}
+
+extern "C" int mrirt_siren_backward(const MrirtInrDesc* desc, const float* w_f32, int64_t n, const float* dlogits, float* grad_w,
+                                    float* grad_b, uint32_t flags, void* scratch, int64_t scratch_bytes, void* stream) {
+    return backward_f32(desc, true, w_f32, n, dlogits, grad_w, grad_b, flags, scratch, scratch_bytes, stream);
 }

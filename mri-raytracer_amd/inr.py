@@ -12,6 +12,7 @@ model_load, predict_volume``: inr/interactive.ipynb cell 5, inr/viewer/brats_vie
   make_loss_and_grad(num_classes, class_weights, dice_weight, K)        model.py:57-90      (csrc/inr_train.hip)
   train_inr(config, cases_or_cache, ...) -> (params, state)             train.py:18-259     (csrc/inr_optim.hip)
   VoxelCache(cases).sample(seed, batch_index, n) / .sample_voxels(...)  dataloader.py:86-96,133-155
+  siren_init / make_siren_loss_and_grad / siren_autograd / train_siren   neumors_inr.ipynb:1150-1200 (csrc/inr_train.hip)
 
 ``params`` is the reference's list of ``{"W": [in,out], "b": [out]}`` (SIREN: dict ``l{i}`` ->
 ``{"w","b"}``).  All arithmetic runs in csrc/inr_mlp.hip (bf16 MFMA, fp32 accumulate, split-bf16
@@ -749,21 +750,24 @@ def train_cfg(micro_batch: int, accum: int, seed: int, class_weights, dice_weigh
 
 
 def train_run(desc: _lib.InrDesc, cache: VoxelCache, cfg: _lib.InrTrainCfg, st: AdamWState, steps: int, scratch: Optional[torch.Tensor] = None):
-    """``mrirt_inr_train_run``: ``steps`` optimiser steps from ``st.step`` on, enqueued in one call without a host
+    """``mrirt_inr_train_run`` (``mrirt_siren_train_run`` for a SIREN descriptor): ``steps`` optimiser steps from ``st.step``
+    on, enqueued in one call without a host
     synchronisation.  Returns the device tensor history (steps, accum, 1 + 2 C): loss, CE per class, Dice per class of every
     micro-batch.  ``st`` is updated in place and ``st.step`` advanced."""
     lib = _lib.lib()
-    nbytes = int(lib.mrirt_inr_train_run_scratch_bytes(C.byref(desc), C.byref(cache.desc), C.byref(cfg)))
+    family = "siren" if int(desc.kind) in (KIND_SIREN, KIND_RAW_SIREN) else "inr"
+    run_bytes, run = getattr(lib, f"mrirt_{family}_train_run_scratch_bytes"), getattr(lib, f"mrirt_{family}_train_run")
+    nbytes = int(run_bytes(C.byref(desc), C.byref(cache.desc), C.byref(cfg)))
     if nbytes <= 0:
-        raise ValueError("train_run: unsupported network / cache / configuration (Fourier ReLU kind over the cache's modalities, "
+        raise ValueError("train_run: unsupported network / cache / configuration (Fourier ReLU or SIREN kind over the cache's modalities, "
                          "accum >= 1, decay_steps > warmup_steps, finite hyper-parameters)")
     if scratch is None or scratch.numel() < nbytes:
         scratch = torch.empty(nbytes, dtype=torch.uint8, device=st.w.device)
     hist = torch.empty((int(steps), int(cfg.accum), 1 + 2 * int(desc.outDim)), dtype=torch.float32, device=st.w.device)
     cs = st.c_state()
-    rc = lib.mrirt_inr_train_run(C.byref(desc), C.byref(cache.desc), C.byref(cfg), C.byref(cs), int(st.step), int(steps), _ptr(hist),
-                                 _ptr(scratch), scratch.numel(), _stream_ptr(None))
-    _lib.check(rc, "mrirt_inr_train_run")
+    rc = run(C.byref(desc), C.byref(cache.desc), C.byref(cfg), C.byref(cs), int(st.step), int(steps), _ptr(hist),
+             _ptr(scratch), scratch.numel(), _stream_ptr(None))
+    _lib.check(rc, f"mrirt_{family}_train_run")
     st.step += int(steps)
     return hist
 
@@ -791,23 +795,12 @@ def _load_resume(path) -> Tuple[List[Dict[str, np.ndarray]], Optional[Dict[str, 
     return params, opt
 
 
-def train_inr(config: Dict[str, Any], cases_or_cache, val_cases=None, params=None, resume_from=None, log=None, save_path=None):
-    """inr/inr/train.py:18-259 on the GPU with the reference's config keys (GLOBAL_BATCH_SIZE, MICRO_BATCH_SIZE, FOURIER_FREQS,
-    HIDDEN_DIMS, LR, MIN_LR, WARMUP_STEPS, TRAIN_STEPS, RNG_SEED, NUM_CLASSES, DICE_WEIGHT, CLASS_WEIGHTS, CLIP_NORM,
-    CHECKPOINT_EVERY_STEPS): ``accum = ceil(global / micro)`` micro-batches per update, clip_by_global_norm + AdamW under the
-    warm-up / cosine schedule, all inside ``mrirt_inr_train_run`` — one call per chunk of steps, a chunk ending at every
-    checkpoint step, and one read-back of the chunk's history.
-
-    ``cases_or_cache``: a ``VoxelCache`` or the list of cases to build one from.  ``params``: initial parameters (default
-    ``init_mlp(RNG_SEED, ...)``).  ``save_path``: a directory; only then ``checkpoint_step{step:06d}.npz`` (``W_i`` / ``b_i``,
-    the reference's periodic layout) is written every CHECKPOINT_EVERY_STEPS steps, with the optimiser moments and the step
-    in ``checkpoint_step{step:06d}_opt.npz`` beside it.  ``resume_from``: such a file (with the moments beside it the run
-    continues at its step and reproduces the uninterrupted run bit for bit; without them it restarts the schedule from the
-    loaded parameters, as the reference does) or a ``model_load`` checkpoint.  ``log(step, metrics)`` is called per step.
-    Returns ``(params, state)``: the reference's list of ``{"W", "b"}`` (NumPy) and a dict with ``loss_history``,
-    ``dice_history`` / ``ce_history`` (per class), the caches, ``vol_shape`` and ``opt`` (the ``AdamWState``)."""
+def _train_loop(config: Dict[str, Any], cases_or_cache, val_cases, params, resume_from, log, save_path, in_dim_of, default_params, make_desc):
+    """The loop ``train_inr`` and ``train_siren`` share: config parsing, cache, resume, chunked ``train_run`` calls, history and
+    checkpoints.  ``in_dim_of(cache)`` -> input width, ``default_params(seed, in_dim, hidden_dims, nc)`` -> initial parameters,
+    ``make_desc(dims, cache)`` -> the training descriptor.  Returns (AdamWState, state dict without "params")."""
     g, micro = int(config["GLOBAL_BATCH_SIZE"]), int(config["MICRO_BATCH_SIZE"])
-    K, hidden_dims = int(config["FOURIER_FREQS"]), [int(h) for h in config["HIDDEN_DIMS"]]
+    hidden_dims = [int(h) for h in config["HIDDEN_DIMS"]]
     warmup, train_steps = int(config["WARMUP_STEPS"]), int(config["TRAIN_STEPS"])
     nc, seed = int(config["NUM_CLASSES"]), int(config["RNG_SEED"])
     every = int(config.get("CHECKPOINT_EVERY_STEPS", 200))
@@ -818,12 +811,14 @@ def train_inr(config: Dict[str, Any], cases_or_cache, val_cases=None, params=Non
     lr_schedule(float(config["LR"]), float(config["MIN_LR"]), warmup, decay_steps, 0)          # refuses T <= 0 before any work
     cache = cases_or_cache if isinstance(cases_or_cache, VoxelCache) else VoxelCache(cases_or_cache)
     val_cache = None if val_cases is None else (val_cases if isinstance(val_cases, VoxelCache) else VoxelCache(val_cases))
-    in_dim = 3 + 6 * K + cache.n_modalities
+    in_dim = in_dim_of(cache)
     opt = None
     if resume_from is not None:
         params, opt = _load_resume(resume_from)
     elif params is None:
-        params = init_mlp(seed, in_dim, hidden_dims, nc)
+        params = default_params(seed, in_dim, hidden_dims, nc)
+    if isinstance(params, dict):                         # the SIREN notebook layout
+        params = [{"W": W, "b": b} for W, b in _layers(params)]
     st = AdamWState.from_params(params, cache.device)
     if st.dims != [in_dim] + hidden_dims + [nc]:
         raise ValueError(f"the parameters have layer widths {st.dims}, the config asks for {[in_dim] + hidden_dims + [nc]}")
@@ -831,7 +826,7 @@ def train_inr(config: Dict[str, Any], cases_or_cache, val_cases=None, params=Non
         for k in ("mu_w", "mu_b", "nu_w", "nu_b"):
             getattr(st, k).copy_(torch.from_numpy(np.asarray(opt[k], np.float32)))
         st.step = int(opt["step"])
-    desc = train_desc(st.dims, K, cache.n_modalities)
+    desc = make_desc(st.dims, cache)
     cfg = train_cfg(micro, accum, seed, config["CLASS_WEIGHTS"], float(config["DICE_WEIGHT"]), float(config["LR"]), float(config["MIN_LR"]),
                     warmup, decay_steps, float(config["CLIP_NORM"]))
     if save_path is not None:
@@ -840,7 +835,8 @@ def train_inr(config: Dict[str, Any], cases_or_cache, val_cases=None, params=Non
     loss_history: List[float] = []
     dice_history: List[List[float]] = [[] for _ in range(nc)]
     ce_history: List[List[float]] = [[] for _ in range(nc)]
-    nbytes = int(_lib.lib().mrirt_inr_train_run_scratch_bytes(C.byref(desc), C.byref(cache.desc), C.byref(cfg)))
+    family = "siren" if int(desc.kind) in (KIND_SIREN, KIND_RAW_SIREN) else "inr"
+    nbytes = int(getattr(_lib.lib(), f"mrirt_{family}_train_run_scratch_bytes")(C.byref(desc), C.byref(cache.desc), C.byref(cfg)))
     scratch = torch.empty(nbytes, dtype=torch.uint8, device=cache.device) if nbytes > 0 else None      # one buffer for every chunk
     while st.step < train_steps:
         first = st.step
@@ -865,8 +861,176 @@ def train_inr(config: Dict[str, Any], cases_or_cache, val_cases=None, params=Non
             np.savez_compressed(ck, **flat)
             np.savez_compressed(ck.with_name(ck.stem + "_opt.npz"), step=np.int64(st.step),
                                 **{k: getattr(st, k).cpu().numpy() for k in ("mu_w", "mu_b", "nu_w", "nu_b")})
-    out = st.params()
-    state = {"params": out, "train_cache": cache, "val_cache": val_cache, "vol_shape": cache.vol_shape, "loss_history": loss_history,
+    state = {"train_cache": cache, "val_cache": val_cache, "vol_shape": cache.vol_shape, "loss_history": loss_history,
              "dice_history": dice_history, "ce_history": ce_history, "best_val_dice": None, "best_step": None, "save_path": save_path,
              "checkpoint_periodic_basename": CHECKPOINT_BASENAME, "opt": st}
+    return st, state
+
+
+def train_inr(config: Dict[str, Any], cases_or_cache, val_cases=None, params=None, resume_from=None, log=None, save_path=None):
+    """inr/inr/train.py:18-259 on the GPU with the reference's config keys (GLOBAL_BATCH_SIZE, MICRO_BATCH_SIZE, FOURIER_FREQS,
+    HIDDEN_DIMS, LR, MIN_LR, WARMUP_STEPS, TRAIN_STEPS, RNG_SEED, NUM_CLASSES, DICE_WEIGHT, CLASS_WEIGHTS, CLIP_NORM,
+    CHECKPOINT_EVERY_STEPS): ``accum = ceil(global / micro)`` micro-batches per update, clip_by_global_norm + AdamW under the
+    warm-up / cosine schedule, all inside ``mrirt_inr_train_run`` — one call per chunk of steps, a chunk ending at every
+    checkpoint step, and one read-back of the chunk's history.
+
+    ``cases_or_cache``: a ``VoxelCache`` or the list of cases to build one from.  ``params``: initial parameters (default
+    ``init_mlp(RNG_SEED, ...)``).  ``save_path``: a directory; only then ``checkpoint_step{step:06d}.npz`` (``W_i`` / ``b_i``,
+    the reference's periodic layout) is written every CHECKPOINT_EVERY_STEPS steps, with the optimiser moments and the step
+    in ``checkpoint_step{step:06d}_opt.npz`` beside it.  ``resume_from``: such a file (with the moments beside it the run
+    continues at its step and reproduces the uninterrupted run bit for bit; without them it restarts the schedule from the
+    loaded parameters, as the reference does) or a ``model_load`` checkpoint.  ``log(step, metrics)`` is called per step.
+    Returns ``(params, state)``: the reference's list of ``{"W", "b"}`` (NumPy) and a dict with ``loss_history``,
+    ``dice_history`` / ``ce_history`` (per class), the caches, ``vol_shape`` and ``opt`` (the ``AdamWState``)."""
+    K = int(config["FOURIER_FREQS"])
+    st, state = _train_loop(config, cases_or_cache, val_cases, params, resume_from, log, save_path,
+                            lambda cache: 3 + 6 * K + cache.n_modalities, init_mlp,
+                            lambda dims, cache: train_desc(dims, K, cache.n_modalities))
+    out = st.params()
+    state = {"params": out, **state}
+    return out, state
+
+
+# --- SIREN training: the exact-sine fp32 step and loop (csrc/inr_train.hip, csrc/siren_sincos.h; DESIGN.md section 16) ----------
+def siren_init(seed: int, in_dim: int, hidden_dims: Sequence[int], out_dim: int, w0: float = 30.0) -> Dict[str, Dict[str, np.ndarray]]:
+    """neumors_inr.ipynb:1150-1163 with a NumPy generator: layer 0 ~ U(+-sqrt(6 / in) / w0), every later layer (the head
+    included) ~ U(+-sqrt(6 / in)), zero biases; the notebook's dict ``l{i} -> {"w", "b"}`` (jax's key stream is not reproduced)."""
+    rng = np.random.default_rng(int(seed))
+    dims = [int(in_dim)] + [int(h) for h in hidden_dims] + [int(out_dim)]
+    params = {}
+    for i, (a, b) in enumerate(zip(dims[:-1], dims[1:])):
+        lim = np.sqrt(6.0 / a) / (float(w0) if i == 0 else 1.0)
+        params[f"l{i}"] = {"w": rng.uniform(-lim, lim, (a, b)).astype(np.float32), "b": np.zeros(b, np.float32)}
+    return params
+
+
+def siren_train_desc(dims: Sequence[int], num_mods: Optional[int] = None, w0: float = 30.0) -> _lib.InrDesc:
+    """Descriptor of a SIREN ``dims = [in, hidden, .., hidden, out]`` for the ``mrirt_siren_*`` entry points: ``num_mods=None``
+    is the raw kind (the input matrix is given), otherwise x = (coords, ``num_mods`` intensities) and ``in`` must be
+    ``3 + num_mods``."""
+    dims = [int(v) for v in dims]
+    if len(dims) < 3 or any(v != dims[1] for v in dims[1:-1]):
+        raise ValueError(f"layer widths {dims}: the kernels need at least one hidden layer and equal hidden widths")
+    if num_mods is not None and dims[0] != 3 + int(num_mods):
+        raise ValueError(f"a SIREN over {num_mods} modalities has {3 + int(num_mods)} inputs, not {dims[0]}")
+    if not np.isfinite(w0) or float(w0) == 0.0:
+        raise ValueError("w0 must be finite and non-zero")
+    d = _lib.InrDesc()
+    d.kind = KIND_RAW_SIREN if num_mods is None else KIND_SIREN
+    d.numLayers, d.inDim, d.hidden, d.outDim = len(dims) - 1, dims[0], dims[1], dims[-1]
+    d.fourierFreqs, d.numMods, d.w0 = 0, (0 if num_mods is None else int(num_mods)), float(w0)
+    return d
+
+
+def siren_train_scratch(desc: _lib.InrDesc, n: int, dev) -> torch.Tensor:
+    nbytes = int(_lib.lib().mrirt_siren_train_scratch_bytes(C.byref(desc), int(n)))
+    if nbytes <= 0:
+        raise ValueError(f"unsupported SIREN training shape: in {desc.inDim}, hidden {desc.hidden} x {desc.numLayers - 1}, out {desc.outDim}, "
+                         f"n {n} (SIREN kinds, hidden in {{32,64,128,256}}, in <= 128, out <= 16, <= 8 layers, n >= 1, finite w0 != 0)")
+    return torch.empty(nbytes, dtype=torch.uint8, device=dev)
+
+
+def siren_forward_f32(desc: _lib.InrDesc, w_flat: torch.Tensor, b_flat: torch.Tensor, coords, feats, n: int, scratch: torch.Tensor):
+    """``mrirt_siren_forward_f32``: fp32 logits (n, out); inputs, sines and cosines stay in ``scratch`` for the backward."""
+    logits = torch.empty((int(n), int(desc.outDim)), dtype=torch.float32, device=w_flat.device)
+    rc = _lib.lib().mrirt_siren_forward_f32(C.byref(desc), _ptr(w_flat), _ptr(b_flat), _ptr(coords), _ptr(feats), int(n), _ptr(logits),
+                                            _ptr(scratch), scratch.numel(), _stream_ptr(None))
+    _lib.check(rc, "mrirt_siren_forward_f32")
+    return logits
+
+
+def siren_backward_f32(desc: _lib.InrDesc, w_flat: torch.Tensor, n: int, dlogits: torch.Tensor, scratch: torch.Tensor,
+                       grad_w: Optional[torch.Tensor] = None, grad_b: Optional[torch.Tensor] = None, accumulate: bool = False):
+    """``mrirt_siren_backward``: (grad_w, grad_b) in the flat layouts, from what ``siren_forward_f32`` left in ``scratch``."""
+    nb = int(desc.hidden) * (int(desc.numLayers) - 1) + int(desc.outDim)
+    gw = grad_w if grad_w is not None else torch.empty_like(w_flat)
+    gb = grad_b if grad_b is not None else torch.empty(nb, dtype=torch.float32, device=w_flat.device)
+    rc = _lib.lib().mrirt_siren_backward(C.byref(desc), _ptr(w_flat), int(n), _ptr(dlogits), _ptr(gw), _ptr(gb), 1 if accumulate else 0,
+                                         _ptr(scratch), scratch.numel(), _stream_ptr(None))
+    _lib.check(rc, "mrirt_siren_backward")
+    return gw, gb
+
+
+def _siren_dict(layers) -> Dict[str, Dict[str, Any]]:
+    return {f"l{i}": {"w": p["W"], "b": p["b"]} for i, p in enumerate(layers)}
+
+
+def make_siren_loss_and_grad(num_classes: int, class_weights, dice_weight: float, w0: float = 30.0):
+    """``make_loss_and_grad`` for the notebook's SIREN: ``f(params, coords, intensities, labels) -> ((loss, aux), grads)`` with
+    ``params`` the dict ``l{i} -> {"w", "b"}`` and ``grads`` a dict of device tensors shaped like it.  x = (coords, intensities)."""
+    cw = [float(v) for v in np.asarray(class_weights, dtype=np.float32).reshape(-1)]
+    if len(cw) != int(num_classes):
+        raise ValueError(f"class_weights holds {len(cw)} values for {num_classes} classes")
+
+    def loss_and_grad(params, coords, intensities, labels):
+        dev = _require_gpu()
+        layers = [(params[f"l{i}"]["w"], params[f"l{i}"]["b"]) for i in range(len(params))]
+        Ws, bs = [_dev_f32(W, dev) for W, _ in layers], [_dev_f32(b, dev) for _, b in layers]
+        dims = _param_dims(Ws, bs)
+        if dims[-1] != int(num_classes):
+            raise ValueError(f"the network has {dims[-1]} outputs for {num_classes} classes")
+        c, f = _dev_f32(coords, dev), (_dev_f32(intensities, dev) if intensities is not None else None)
+        n = int(c.shape[0])
+        lab = torch.as_tensor(labels).to(dev).to(torch.int32).contiguous()
+        desc = siren_train_desc(dims, f.shape[1] if f is not None and f.dim() == 2 else 0, w0)
+        w_flat, b_flat = torch.cat([W.reshape(-1) for W in Ws]), torch.cat(bs)
+        scratch = siren_train_scratch(desc, n, dev)
+        logits = siren_forward_f32(desc, w_flat, b_flat, c, f, n, scratch)
+        loss, aux, dl = loss_and_dlogits(logits, lab, cw, dice_weight, scratch)
+        gw, gb = siren_backward_f32(desc, w_flat, n, dl, scratch)
+        return (loss, {"ce_per_class": aux[0], "dice_per_class": aux[1]}), _siren_dict(_split_grads(gw, gb, dims))
+
+    return loss_and_grad
+
+
+class _SirenF32(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, coords, feats, w0, num_layers, *wb):
+        Ws, bs = wb[:num_layers], wb[num_layers:]
+        dims = _param_dims(Ws, bs)
+        dev = Ws[0].device
+        raw = coords is None
+        n = int(feats.shape[0]) if raw else int(coords.shape[0])
+        desc = siren_train_desc(dims, None if raw else (feats.shape[1] if feats is not None else 0), w0)
+        w_flat = torch.cat([W.detach().to(torch.float32).reshape(-1) for W in Ws])
+        b_flat = torch.cat([b.detach().to(torch.float32).reshape(-1) for b in bs])
+        scratch = siren_train_scratch(desc, n, dev)
+        logits = siren_forward_f32(desc, w_flat, b_flat, coords, feats, n, scratch)
+        ctx.desc, ctx.dims, ctx.n, ctx.w_flat, ctx.scratch = desc, dims, n, w_flat, scratch
+        return logits
+
+    @staticmethod
+    def backward(ctx, grad_logits):
+        gw, gb = siren_backward_f32(ctx.desc, ctx.w_flat, ctx.n, grad_logits.to(torch.float32).contiguous(), ctx.scratch)
+        g = _split_grads(gw, gb, ctx.dims)
+        return (None, None, None, None, *[x["W"] for x in g], *[x["b"] for x in g])
+
+
+def siren_autograd(ws, bs, coords, feats, w0: float = 30.0) -> torch.Tensor:
+    """Differentiable fp32 logits (n, out) of a SIREN: forward ``mrirt_siren_forward_f32``, backward ``mrirt_siren_backward``;
+    gradients reach ``ws`` (each (in, out)) and ``bs`` only.  ``coords=None``: ``feats`` is the (n, in) input matrix; otherwise
+    x = (coords (n, 3), intensities ``feats`` (n, M))."""
+    dev = ws[0].device
+    c = _dev_f32(coords, dev) if coords is not None else None
+    f = _dev_f32(feats, dev) if feats is not None else None
+    return _SirenF32.apply(c, f, float(w0), len(ws), *ws, *bs)
+
+
+def train_siren(config: Dict[str, Any], cases_or_cache, val_cases=None, params=None, resume_from=None, log=None, save_path=None):
+    """``train_inr`` for the notebook's SIREN (x = (coords, modalities), neumors_inr.ipynb:1150-1200): the same config keys
+    without FOURIER_FREQS, plus ``W0`` (default 30); the same chunking, the same ``W_i`` / ``b_i`` + ``_opt.npz`` checkpoints
+    and the same bit-for-bit resume, all inside ``mrirt_siren_train_run``.  ``params``: the notebook's dict ``l{i} -> {"w", "b"}``
+    (default ``siren_init(RNG_SEED, ...)``).  Returns ``(params dict, state)``; the dict goes into
+    ``pack_mlp(params, KIND_SIREN, 0, M, w0)`` as it is."""
+    w0 = float(config.get("W0", 30.0))
+    if not np.isfinite(w0) or w0 == 0.0:
+        raise ValueError("W0 must be finite and non-zero")
+    if "FOURIER_FREQS" in config and int(config["FOURIER_FREQS"]) != 0:
+        raise ValueError("a SIREN takes no Fourier features: drop FOURIER_FREQS (or set it to 0)")
+    st, state = _train_loop(config, cases_or_cache, val_cases, params, resume_from, log, save_path,
+                            lambda cache: 3 + cache.n_modalities,
+                            lambda seed, in_dim, hidden_dims, nc: siren_init(seed, in_dim, hidden_dims, nc, w0),
+                            lambda dims, cache: siren_train_desc(dims, cache.n_modalities, w0))
+    out = _siren_dict(st.params())
+    state = {"params": out, "w0": w0, **state}
     return out, state

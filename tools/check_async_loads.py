@@ -247,7 +247,8 @@ def hazard_scan(name, lines):
 # padding between an MFMA and the first VALU / LDS / vector-memory instruction that reads or overwrites its result (gfx940 family:
 # passes + 3 wait states — 11 for the 8-pass 32x32x16 bf16 product; hipcc keeps 12 in the kernels it schedules itself) is the
 # kernel author's job there.  Same lesson as the SGPR hazard above: what the compiler cannot see, the build checks.  Counted
-# as LLVM counts them (one per instruction, N + 1 per s_nop N), in layout order inside a function.
+# as LLVM counts them (one per instruction, N + 1 per s_nop N), in layout order inside a function; an unconditional branch
+# ends the run (the next instruction in the layout does not execute after it).
 VREG = re.compile(r"\b([va])\[(\d+):(\d+)\]|\b([va])(\d+)\b")
 MFMA_RESULT_WAIT_STATES = 11
 
@@ -284,6 +285,9 @@ def mfma_result_scan(name, lines):
                         break
             for r in dst:
                 last[r] = i
+            continue
+        if mn in ("s_branch", "s_endpgm", "s_setpc_b64"):         # no fall-through: what follows in the layout is another
+            last.clear()                                           # path's block (a loop's s_branch back, then the K = 0 zero fill)
             continue
         if mn.startswith("s_") or not ops:
             continue

@@ -8,7 +8,12 @@ AdamW (csrc/inr_optim.hip), all enqueued by ``mrirt_inr_train_run`` in chunks of
 clipping.  Loss and per-class Dice of the whole volume are printed before and after; the fitted weights then go through
 ``pack_mlp`` and ``predict_volume``, the bf16 inference path, whose Dice against the labels is the last line.
 
+``--siren`` fits the notebook's SIREN instead (x = (coords, modalities), ``mrirt.inr.train_siren`` / ``mrirt_siren_train_run``,
+the exact-sine step of DESIGN.md section 16); the fitted dict goes through ``pack_mlp(params, KIND_SIREN, 0, 4, w0)`` and
+``classify``, and the Dice of those classes against the labels is the last line.
+
     python tools/inr_fit.py [--size 48] [--steps 300] [--batch 4096] [--hidden 64] [--layers 4] [--freqs 4] [--lr 3e-3]
+    python tools/inr_fit.py --siren [--w0 30] [--lr 1e-3] ...
 """
 import argparse
 import pathlib
@@ -31,6 +36,8 @@ def main():
     ap.add_argument("--lr", type=float, default=3e-3)
     ap.add_argument("--dice-weight", type=float, default=0.5)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--siren", action="store_true", help="fit a SIREN (sine activations) instead of the Fourier/ReLU network")
+    ap.add_argument("--w0", type=float, default=30.0)
     args = ap.parse_args()
     import torch
     from mrirt import inr, synth
@@ -47,6 +54,8 @@ def main():
     counts = np.bincount(seg.reshape(-1), minlength=nc).astype(np.float64)
     cw = (counts.sum() / (nc * np.maximum(counts, 1.0))).astype(np.float32)          # inverse-frequency class weights
 
+    if args.siren:
+        return fit_siren(args, inr, dev, mods, seg, coords, feats, labels, cw, nc)
     params = [{k: torch.from_numpy(v).to(dev) for k, v in p.items()} for p in inr.init_mlp(args.seed, 3 + 6 * K + 4, [args.hidden] * args.layers, nc)]
     step = inr.make_loss_and_grad(nc, cw, args.dice_weight, K)
     config = dict(GLOBAL_BATCH_SIZE=args.batch, MICRO_BATCH_SIZE=args.batch, FOURIER_FREQS=K, HIDDEN_DIMS=[args.hidden] * args.layers, LR=args.lr,
@@ -69,6 +78,31 @@ def main():
     pred, _ = inr.predict_volume(host, {"mods": mods, "seg": seg}, K, net=net)
     dice = inr.dice_score(pred, torch.from_numpy(seg).to(dev), nc)
     print("predict_volume (bf16 inference path) dice per class:", {c: round(v, 4) for c, v in dice.items()})
+
+
+def fit_siren(args, inr, dev, mods, seg, coords, feats, labels, cw, nc):
+    import torch
+    params = inr.siren_init(args.seed, 7, [args.hidden] * args.layers, nc, args.w0)
+    step = inr.make_siren_loss_and_grad(nc, cw, args.dice_weight, args.w0)
+    config = dict(GLOBAL_BATCH_SIZE=args.batch, MICRO_BATCH_SIZE=args.batch, HIDDEN_DIMS=[args.hidden] * args.layers, LR=args.lr, MIN_LR=args.lr,
+                  WARMUP_STEPS=0, TRAIN_STEPS=args.steps, RNG_SEED=args.seed, NUM_CLASSES=nc, DICE_WEIGHT=args.dice_weight,
+                  CLASS_WEIGHTS=[float(v) for v in cw], CLIP_NORM=float("inf"), CHECKPOINT_EVERY_STEPS=100, W0=args.w0)
+
+    def whole_volume(tag, p):
+        (loss, aux), _ = step(p, coords, feats, labels)
+        print(f"{tag}: loss {float(loss):.4f}  soft dice per class {[round(float(v), 4) for v in aux['dice_per_class'].cpu()]}"
+              f"  ce per class {[round(float(v), 4) for v in aux['ce_per_class'].cpu()]}")
+    whole_volume("before", params)
+
+    def log(it, m):
+        if it % 100 == 0:
+            print(f"step {it}: batch loss {m['train/loss']:.4f}")
+    params, _ = inr.train_siren(config, [{"mods": mods, "seg": seg}], params=params, log=log)
+    whole_volume("after", params)
+    net = inr.pack_mlp(params, inr.KIND_SIREN, 0, 4, args.w0)
+    pred = inr.classify(net, coords, feats).reshape(seg.shape)
+    dice = inr.dice_score(pred, torch.from_numpy(seg).to(dev), nc)
+    print("classify (bf16 inference path) dice per class:", {c: round(v, 4) for c, v in dice.items()})
 
 
 if __name__ == "__main__":
