@@ -36,7 +36,9 @@ extern "C" {
  *    mrirt_inr_sample_batch, mrirt_inr_adamw_scratch_bytes, mrirt_inr_adamw_step, mrirt_inr_lr_schedule,
  *    mrirt_inr_train_run_scratch_bytes, mrirt_inr_train_run;
  *    SIREN training (no new struct): mrirt_siren_train_scratch_bytes, mrirt_siren_forward_f32, mrirt_siren_backward,
- *    mrirt_siren_train_run_scratch_bytes, mrirt_siren_train_run. */
+ *    mrirt_siren_train_run_scratch_bytes, mrirt_siren_train_run;
+ *    Muon: MrirtMuon (mrirt_sizeof(11)), mrirt_muon_scratch_bytes, mrirt_muon_orthogonalize, mrirt_muon_step,
+ *    mrirt_inr_train_run_muon_scratch_bytes, mrirt_inr_train_run_muon. */
 #define MRIRT_ABI_VERSION 4
 
 typedef enum MrirtStatus {
@@ -551,6 +553,48 @@ int mrirt_siren_train_run(const MrirtInrDesc* desc, const MrirtInrCache* cache, 
                           int64_t scratch_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------ */
+/* Muon for INR training (notebooks/neumors_inr.ipynb:1191-1192: optax.contrib.muon).    */
+/* Added within ABI 4: new symbols and one new struct only, mrirt_sizeof(11)             */
+/* ------------------------------------------------------------------------------------ */
+/* Muon (Jordan et al. 2024) as optax's scale_by_muon states it, for the weight matrices of a network of shape `desc` (any
+ * kind the training entry points take; only numLayers, inDim, hidden, outDim matter); the biases take AdamW.  optax's
+ * defaults: beta 0.95, nesterov 1, nsSteps 5, nsCoeffs (3.4445, -4.7750, 2.0315), eps 1e-8, weightDecay 0. */
+typedef struct MrirtMuon {
+    float beta, eps, weightDecay;
+    float nsCoeffs[3];           /* c0, c1, c2 of X <- c0 X + (c1 A + c2 A A) X, A = X X^T */
+    uint32_t nsSteps, nesterov;
+} MrirtMuon;
+/* Update number t (0-based) of W[in][out] (flat row-major layout of mrirt_inr_forward_f32), with g' = (g gscale) s and s the
+ * clip factor of mrirt_inr_adamw_step over ALL gradients (same kernels, same gnorm[2]); every operation below is one fp32
+ * rounding unless said otherwise, in the order written:
+ *   mu  <- beta mu + omb g'                        omb = float(1 - beta), c1 = float(1 - beta^(t+1)), c2 = float(1 - beta^(t+2)),
+ *   m^   = beta (mu / c2) + omb (g' / c1)          evaluated in fp64 on the host;  without nesterov m^ = mu / c1
+ *   X    = float(double(m^) / (sqrt(sum m^^2) + double(eps)))      the sum in fp64 in a fixed order; X^T when in > out
+ *   nsSteps times: A = X X^T;  B = c1 A + c2 (A A);  X <- c0 X + (B X)      the sums on the fp32 MFMA, increasing k
+ *   W   <- W - lr (float(sqrt(max(1, out / in))) O + weightDecay W)          O = X, transposed back
+ * Biases: adamw_one of mrirt_inr_adamw_step with adamw's b1, b2, eps, weightDecay and the same s, lr, t.  adamw also supplies
+ * lr and clipNorm.  There is no second moment of the weights.
+ * mrirt_muon_orthogonalize: out_flat = NS(m_flat) for every layer's matrix in one call (out_flat may be m_flat; neither may
+ * overlap scratch).  An all-zero matrix gives zeros; a NaN anywhere in a matrix makes that layer's output NaN, not the others'.
+ * mrirt_muon_scratch_bytes: device bytes either call needs (0 for a shape the training entry points refuse).
+ * Checks before any launch: MRIRT_ERR_NULL; MRIRT_ERR_ARG for beta outside [0, 1), eps not finite or <= 0, non-finite
+ * nsCoeffs / weightDecay / gscale, nsSteps outside 1..16, nesterov > 1, what mrirt_inr_adamw_step refuses of `adamw`, a
+ * scratch that is not 16-byte aligned or too small, a refused shape.  No allocation, no host synchronisation, no float
+ * atomics: the same inputs give the same bits. */
+int64_t mrirt_muon_scratch_bytes(const MrirtInrDesc* desc);
+int mrirt_muon_orthogonalize(const MrirtInrDesc* desc, const float* m_flat, float* out_flat, const MrirtMuon* hp, void* scratch,
+                             int64_t scratch_bytes, void* stream);
+int mrirt_muon_step(const MrirtInrDesc* desc, float* w, float* b, const float* gw, const float* gb, float* mu_w, float* mu_b,
+                    float* nu_b, const MrirtMuon* hp, const MrirtAdamW* adamw, uint64_t t, float gscale, double* gnorm,
+                    void* scratch, int64_t scratch_bytes, void* stream);
+/* mrirt_inr_train_run / mrirt_siren_train_run (by desc->kind: MRIRT_INR_FOURIER_RELU or MRIRT_INR_SIREN) with
+ * mrirt_muon_step in place of mrirt_inr_adamw_step; cfg->adamw is the bias / clip half; state->nu_w is not touched. */
+int64_t mrirt_inr_train_run_muon_scratch_bytes(const MrirtInrDesc* desc, const MrirtInrCache* cache, const MrirtInrTrainCfg* cfg);
+int mrirt_inr_train_run_muon(const MrirtInrDesc* desc, const MrirtInrCache* cache, const MrirtInrTrainCfg* cfg, const MrirtMuon* hp,
+                             const MrirtInrTrainState* state, uint64_t first_step, uint32_t steps, float* history, void* scratch,
+                             int64_t scratch_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------ */
 /* Exact distance transform and Hausdorff distance (inr/inr/model.py:164-195)            */
 /* ------------------------------------------------------------------------------------ */
 /* labels / pred / truth: the int16 [H][W][D] C-order volume mrirt_inr_predict_volume writes (device).  The coordinate of
@@ -659,7 +703,8 @@ int mrirt_abi_version(void);
 const char* mrirt_status_string(int status);
 int mrirt_last_hip_error(void);            /* hipError_t of the last failed HIP call on this thread */
 uint32_t mrirt_sizeof(uint32_t which);     /* 0 BratsParams, 1 RenderExt, 2 VolumeParams, 3 SdfParams, 4 InrDesc, 5 Skip,
-                                              6 MeshParams, 7 InrCache, 8 AdamW, 9 InrTrainCfg, 10 InrTrainState */
+                                              6 MeshParams, 7 InrCache, 8 AdamW, 9 InrTrainCfg, 10 InrTrainState,
+                                              11 Muon */
 /* Opt-in diagnostics (host only; the library installs nothing by itself): a SIGABRT handler that writes the native
  * backtrace of the aborting thread and, when file descriptor 2 has been redirected into a regular file (a test runner's
  * capture), the tail of that file to `fd` — a descriptor the caller duplicated before the redirection — and then chains

@@ -17,7 +17,7 @@ CSRC = PKG_DIR / "csrc"
 INCLUDE = PKG_DIR.parent / "include"
 SO_PATH = pathlib.Path(os.environ.get("MRIRT_LIB", PKG_DIR / "libmrirt.so"))   # override: A/B builds in development
 HIP_SOURCES = ["brats_march.hip", "brats_skip.hip", "brats_c5.hip", "brats_slab.hip", "brats_ring.hip", "brats_backward.hip", "volume_march.hip", "grid_ops.hip", "inr_mlp.hip",
-               "inr_train.hip", "inr_optim.hip", "mesh_rt.hip", "edt.hip", "surface.hip", "abort_trace.cpp"]
+               "inr_train.hip", "inr_optim.hip", "inr_muon.hip", "mesh_rt.hip", "edt.hip", "surface.hip", "abort_trace.cpp"]
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17", "-Wall"]
 
 # every extern "C" symbol include/mrirt.h declares
@@ -37,6 +37,8 @@ ABI_SYMBOLS = [
     "mrirt_inr_train_run_scratch_bytes", "mrirt_inr_train_run",
     "mrirt_siren_train_scratch_bytes", "mrirt_siren_forward_f32", "mrirt_siren_backward",
     "mrirt_siren_train_run_scratch_bytes", "mrirt_siren_train_run",
+    "mrirt_muon_scratch_bytes", "mrirt_muon_orthogonalize", "mrirt_muon_step",
+    "mrirt_inr_train_run_muon_scratch_bytes", "mrirt_inr_train_run_muon",
 ]
 
 ABI_VERSION = 4          # MRIRT_ABI_VERSION of include/mrirt.h this binding was written against
@@ -135,6 +137,11 @@ class InrTrainCfg(C.Structure):
 
 class InrTrainState(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("w", "b", "mu_w", "mu_b", "nu_w", "nu_b")]
+
+
+class Muon(C.Structure):
+    """MrirtMuon: the hyper-parameters of optax's scale_by_muon."""
+    _fields_ = [("beta", f32), ("eps", f32), ("weightDecay", f32), ("nsCoeffs", f32 * 3), ("nsSteps", u32), ("nesterov", u32)]
 
 
 class Skip(C.Structure):
@@ -374,6 +381,17 @@ def lib() -> C.CDLL:
     for twin in ("train_scratch_bytes", "forward_f32", "backward", "train_run_scratch_bytes", "train_run"):     # the SIREN twins
         src, dst = getattr(l, "mrirt_inr_" + twin), getattr(l, "mrirt_siren_" + twin)
         dst.argtypes, dst.restype = src.argtypes, src.restype
+    l.mrirt_muon_scratch_bytes.argtypes = [C.POINTER(InrDesc)]
+    l.mrirt_muon_scratch_bytes.restype = i64
+    l.mrirt_muon_orthogonalize.argtypes = [C.POINTER(InrDesc), vp, vp, C.POINTER(Muon), vp, i64, vp]
+    l.mrirt_muon_orthogonalize.restype = i32
+    l.mrirt_muon_step.argtypes = [C.POINTER(InrDesc), vp, vp, vp, vp, vp, vp, vp, C.POINTER(Muon), C.POINTER(AdamW), u64, f32, vp, vp, i64, vp]
+    l.mrirt_muon_step.restype = i32
+    l.mrirt_inr_train_run_muon_scratch_bytes.argtypes = [C.POINTER(InrDesc), C.POINTER(InrCache), C.POINTER(InrTrainCfg)]
+    l.mrirt_inr_train_run_muon_scratch_bytes.restype = i64
+    l.mrirt_inr_train_run_muon.argtypes = [C.POINTER(InrDesc), C.POINTER(InrCache), C.POINTER(InrTrainCfg), C.POINTER(Muon),
+                                           C.POINTER(InrTrainState), u64, u32, vp, vp, i64, vp]
+    l.mrirt_inr_train_run_muon.restype = i32
     l.mrirt_status_string.argtypes = [i32]
     l.mrirt_status_string.restype = C.c_char_p
     l.mrirt_sizeof.argtypes = [u32]
@@ -387,7 +405,7 @@ def lib() -> C.CDLL:
         raise ImportError(f"ABI mismatch: {SO_PATH} reports version {l.mrirt_abi_version()}, this binding expects {ABI_VERSION} "
                           "(rebuild: python -c \"import __graft_entry__ as g; g.build()\")")
     for which, st in enumerate((BratsParams, RenderExt, VolumeParams, SdfParams, InrDesc, Skip, MeshParams, InrCache, AdamW, InrTrainCfg,
-                                InrTrainState)):
+                                InrTrainState, Muon)):
         if l.mrirt_sizeof(which) != C.sizeof(st):
             raise ImportError(f"ABI mismatch: {st.__name__} is {C.sizeof(st)} B here, {l.mrirt_sizeof(which)} B in {SO_PATH}")
     _LIB = l

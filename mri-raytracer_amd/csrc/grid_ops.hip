@@ -450,6 +450,7 @@ extern "C" uint32_t mrirt_sizeof(uint32_t which) {
         case 8: return (uint32_t)sizeof(MrirtAdamW);
         case 9: return (uint32_t)sizeof(MrirtInrTrainCfg);
         case 10: return (uint32_t)sizeof(MrirtInrTrainState);
+        case 11: return (uint32_t)sizeof(MrirtMuon);
         default: return 0;
     }
 }

@@ -6,6 +6,8 @@
 //   adamw_kernel           clip + AdamW on weights and biases in one launch; reads s from the device
 //   mrirt_inr_train_run    enqueues whole optimiser steps (accum x (sample, forward, loss, backward), one update) through the
 //                          same entry points a caller would use one by one: no host synchronisation, no allocation
+//   mrirt_inr_train_run_muon  the same run with mrirt_muon_step (csrc/inr_muon.hip) as the update; that step borrows the norm
+//                          pass and the bias update from here (opt_norm_and_bias_step)
 // No float atomics and no data-dependent order anywhere: the same inputs give the same bits.
 #include "inr_optim.h"
 #include "mrirt_host.h"
@@ -151,6 +153,50 @@ static int check_opt_scratch(const void* scratch, int64_t have, uint64_t need) {
 
 static bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
+// the arguments of one update: the norm runs over [gw | gb] (nw + nb elements), the update over the first nwUpdate weights
+// (all of them, or none) and every bias
+static OptArgs opt_args(float* w, float* b, const float* gw, const float* gb, float* mu_w, float* mu_b, float* nu_w, float* nu_b,
+                        int64_t nw, int64_t nb, int64_t nwUpdate, const MrirtAdamW* hp, uint64_t t, float gscale, double* gnorm, void* scratch) {
+    OptArgs a = {};
+    a.w = w; a.b = b; a.muW = mu_w; a.muB = mu_b; a.nuW = nu_w; a.nuB = nu_b; a.gw = gw; a.gb = gb;
+    a.nw = nw; a.nb = nb;
+    a.units = opt_units(nwUpdate, nb, aligned16(w) && aligned16(gw) && aligned16(mu_w) && aligned16(nu_w),
+                        aligned16(b) && aligned16(gb) && aligned16(mu_b) && aligned16(nu_b));
+    const double b1 = (double)hp->b1, b2 = (double)hp->b2, tp = (double)t + 1.0;
+    a.gscale = gscale; a.lr = hp->lr; a.b1 = hp->b1; a.b2 = hp->b2; a.eps = hp->eps; a.wd = hp->weightDecay;
+    a.omb1 = (float)(1.0 - b1); a.omb2 = (float)(1.0 - b2);
+    a.c1 = (float)(1.0 - pow(b1, tp)); a.c2 = (float)(1.0 - pow(b2, tp));
+    a.clip = (hp->clipNorm > 0.0f && isfinite(hp->clipNorm)) ? (double)hp->clipNorm : 0.0;
+    a.partial = (double*)scratch; a.blocks = opt_blocks(nw + nb);
+    a.gnorm = gnorm;
+    return a;
+}
+
+static int launch_norm(const OptArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(sqnorm_partial_kernel, dim3(a.blocks), dim3(kOptThreads), 0, s, a);
+    MRIRT_HIP(hipGetLastError());
+    hipLaunchKernelGGL(sqnorm_final_kernel, dim3(1), dim3(64), 0, s, a);
+    MRIRT_HIP(hipGetLastError());
+    return MRIRT_OK;
+}
+
+static int launch_adamw(const OptArgs& a, hipStream_t s) {
+    const int64_t units = opt_unit_count(a.units);
+    if (units < 1) return MRIRT_OK;
+    hipLaunchKernelGGL(adamw_kernel, dim3((uint32_t)((units + kOptThreads - 1) / kOptThreads)), dim3(kOptThreads), 0, s, a);
+    MRIRT_HIP(hipGetLastError());
+    return MRIRT_OK;
+}
+
+int opt_check_adamw(const MrirtAdamW* hp, bool needLr) { return check_adamw(hp, needLr); }
+
+int opt_norm_and_bias_step(const float* gw, int64_t nw, float* b, const float* gb, float* mu_b, float* nu_b, int64_t nb,
+                           const MrirtAdamW* hp, uint64_t t, float gscale, double* gnorm, void* scratch, hipStream_t stream) {
+    const OptArgs a = opt_args(nullptr, b, gw, gb, nullptr, mu_b, nullptr, nu_b, nw, nb, 0, hp, t, gscale, gnorm, scratch);
+    const int rc = launch_norm(a, stream);
+    return rc != MRIRT_OK ? rc : launch_adamw(a, stream);
+}
+
 // the shapes, the cache and the configuration of a run; fills the layouts
 static int check_run(const MrirtInrDesc* desc, bool siren, const MrirtInrCache* cache, const MrirtInrTrainCfg* cfg, TrainLayout& L, RunLayout& R) {
     if (!desc || !cache || !cfg) return MRIRT_ERR_NULL;
@@ -208,27 +254,9 @@ extern "C" int mrirt_inr_adamw_step(float* w, float* b, const float* gw, const f
     if (rc != MRIRT_OK) return rc;
     if (!isfinite(gscale) || ((uintptr_t)gnorm & 7u) != 0) return MRIRT_ERR_ARG;
     if ((rc = check_opt_scratch(scratch, scratch_bytes, opt_scratch_bytes(nw + nb))) != MRIRT_OK) return rc;
-    OptArgs a = {};
-    a.w = w; a.b = b; a.muW = mu_w; a.muB = mu_b; a.nuW = nu_w; a.nuB = nu_b; a.gw = gw; a.gb = gb;
-    a.nw = nw; a.nb = nb;
-    a.units = opt_units(nw, nb, aligned16(w) && aligned16(gw) && aligned16(mu_w) && aligned16(nu_w),
-                        aligned16(b) && aligned16(gb) && aligned16(mu_b) && aligned16(nu_b));
-    const double b1 = (double)hp->b1, b2 = (double)hp->b2, tp = (double)t + 1.0;
-    a.gscale = gscale; a.lr = hp->lr; a.b1 = hp->b1; a.b2 = hp->b2; a.eps = hp->eps; a.wd = hp->weightDecay;
-    a.omb1 = (float)(1.0 - b1); a.omb2 = (float)(1.0 - b2);
-    a.c1 = (float)(1.0 - pow(b1, tp)); a.c2 = (float)(1.0 - pow(b2, tp));
-    a.clip = (hp->clipNorm > 0.0f && isfinite(hp->clipNorm)) ? (double)hp->clipNorm : 0.0;
-    a.partial = (double*)scratch; a.blocks = opt_blocks(nw + nb);
-    a.gnorm = gnorm;
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(sqnorm_partial_kernel, dim3(a.blocks), dim3(kOptThreads), 0, s, a);
-    MRIRT_HIP(hipGetLastError());
-    hipLaunchKernelGGL(sqnorm_final_kernel, dim3(1), dim3(64), 0, s, a);
-    MRIRT_HIP(hipGetLastError());
-    const int64_t units = opt_unit_count(a.units);
-    hipLaunchKernelGGL(adamw_kernel, dim3((uint32_t)((units + kOptThreads - 1) / kOptThreads)), dim3(kOptThreads), 0, s, a);
-    MRIRT_HIP(hipGetLastError());
-    return MRIRT_OK;
+    const OptArgs a = opt_args(w, b, gw, gb, mu_w, mu_b, nu_w, nu_b, nw, nb, nw, hp, t, gscale, gnorm, scratch);
+    if ((rc = launch_norm(a, (hipStream_t)stream)) != MRIRT_OK) return rc;
+    return launch_adamw(a, (hipStream_t)stream);
 }
 
 extern "C" int mrirt_inr_lr_schedule(double peak, double end, uint32_t warmup, uint32_t decay_steps, uint64_t t, double* lr) {
@@ -250,6 +278,13 @@ static int64_t run_scratch_bytes(const MrirtInrDesc* desc, bool siren, const Mri
     return check_run(desc, siren, cache, cfg, L, R) == MRIRT_OK ? (int64_t)R.bytes : 0;
 }
 
+// a Muon run's scratch: the AdamW run's, then mrirt_muon_step's
+extern "C" int64_t mrirt_inr_train_run_muon_scratch_bytes(const MrirtInrDesc* desc, const MrirtInrCache* cache, const MrirtInrTrainCfg* cfg) {
+    if (!desc) return 0;
+    const int64_t run = run_scratch_bytes(desc, desc->kind == MRIRT_INR_SIREN, cache, cfg), step = mrirt_muon_scratch_bytes(desc);
+    return run > 0 && step > 0 ? run + step : 0;
+}
+
 extern "C" int64_t mrirt_inr_train_run_scratch_bytes(const MrirtInrDesc* desc, const MrirtInrCache* cache, const MrirtInrTrainCfg* cfg) {
     return run_scratch_bytes(desc, false, cache, cfg);
 }
@@ -258,9 +293,10 @@ extern "C" int64_t mrirt_siren_train_run_scratch_bytes(const MrirtInrDesc* desc,
 }
 
 // One loop for both families: the kind picks the public forward / backward pair, everything else is shared.
+// muon: NULL for AdamW; else the update is mrirt_muon_step, whose scratch lies behind the AdamW run's.
 static int train_run(const MrirtInrDesc* desc, bool siren, const MrirtInrCache* cache, const MrirtInrTrainCfg* cfg,
                      const MrirtInrTrainState* state, uint64_t first_step, uint32_t steps, float* history,
-                     void* scratch, int64_t scratch_bytes, void* stream) {
+                     void* scratch, int64_t scratch_bytes, void* stream, const MrirtMuon* muon = nullptr) {
     TrainLayout L;
     RunLayout R;
     if (!desc || !cache || !cfg || !state || !history) return MRIRT_ERR_NULL;
@@ -268,7 +304,12 @@ static int train_run(const MrirtInrDesc* desc, bool siren, const MrirtInrCache* 
     int rc = check_run(desc, siren, cache, cfg, L, R);
     if (rc != MRIRT_OK) return rc;
     if (steps < 1) return MRIRT_ERR_ARG;
-    if ((rc = check_opt_scratch(scratch, scratch_bytes, R.bytes)) != MRIRT_OK) return rc;
+    const int64_t muonBytes = muon ? mrirt_muon_scratch_bytes(desc) : 0;
+    if (muon) {                                          // what mrirt_muon_step would refuse, before any launch
+        if ((rc = muon_check_hp(muon)) != MRIRT_OK) return rc;
+        if (muonBytes <= 0) return MRIRT_ERR_ARG;
+    }
+    if ((rc = check_opt_scratch(scratch, scratch_bytes, R.bytes + (uint64_t)muonBytes)) != MRIRT_OK) return rc;
     const int64_t n = cfg->microBatch;
     const uint32_t C = desc->outDim;
     char* base = (char*)scratch;
@@ -295,8 +336,13 @@ static int train_run(const MrirtInrDesc* desc, bool siren, const MrirtInrCache* 
         double lr;
         if ((rc = mrirt_inr_lr_schedule(cfg->peakLr, cfg->minLr, cfg->warmupSteps, cfg->decaySteps, t, &lr)) != MRIRT_OK) return rc;
         hp.lr = (float)lr;
-        if ((rc = mrirt_inr_adamw_step(state->w, state->b, gw, gb, state->mu_w, state->mu_b, state->nu_w, state->nu_b, (int64_t)R.nw,
-                                       (int64_t)R.nb, &hp, t, gscale, gnorm, base + R.offOpt, (int64_t)R.optBytes, stream)) != MRIRT_OK) return rc;
+        if (muon)
+            rc = mrirt_muon_step(desc, state->w, state->b, gw, gb, state->mu_w, state->mu_b, state->nu_b, muon, &hp, t, gscale, gnorm,
+                                 base + R.bytes, muonBytes, stream);
+        else
+            rc = mrirt_inr_adamw_step(state->w, state->b, gw, gb, state->mu_w, state->mu_b, state->nu_w, state->nu_b, (int64_t)R.nw,
+                                      (int64_t)R.nb, &hp, t, gscale, gnorm, base + R.offOpt, (int64_t)R.optBytes, stream);
+        if (rc != MRIRT_OK) return rc;
     }
     return MRIRT_OK;
 }
@@ -311,4 +357,11 @@ extern "C" int mrirt_siren_train_run(const MrirtInrDesc* desc, const MrirtInrCac
                                      const MrirtInrTrainState* state, uint64_t first_step, uint32_t steps, float* history,
                                      void* scratch, int64_t scratch_bytes, void* stream) {
     return train_run(desc, true, cache, cfg, state, first_step, steps, history, scratch, scratch_bytes, stream);
+}
+
+extern "C" int mrirt_inr_train_run_muon(const MrirtInrDesc* desc, const MrirtInrCache* cache, const MrirtInrTrainCfg* cfg, const MrirtMuon* hp,
+                                        const MrirtInrTrainState* state, uint64_t first_step, uint32_t steps, float* history,
+                                        void* scratch, int64_t scratch_bytes, void* stream) {
+    if (!desc || !hp) return MRIRT_ERR_NULL;
+    return train_run(desc, desc->kind == MRIRT_INR_SIREN, cache, cfg, state, first_step, steps, history, scratch, scratch_bytes, stream, hp);
 }

@@ -203,4 +203,13 @@ inline void fill_label_addr(LabelAddr& a, const uint32_t dims[3], uint32_t layou
     }
 }
 
+// csrc/inr_optim.hip, for the other optimiser built on its kernels (csrc/inr_muon.hip): the AdamW hyper-parameter check of
+// mrirt_inr_adamw_step, and its norm pass over [gw | gb] (gnorm[0] = norm, gnorm[1] = clip factor) followed by its update
+// kernel on the biases alone.  scratch: opt_scratch_bytes(nw + nb) bytes; nothing is checked here.
+int opt_check_adamw(const MrirtAdamW* hp, bool needLr);
+int opt_norm_and_bias_step(const float* gw, int64_t nw, float* b, const float* gb, float* mu_b, float* nu_b, int64_t nb,
+                           const MrirtAdamW* hp, uint64_t t, float gscale, double* gnorm, void* scratch, hipStream_t stream);
+// csrc/inr_muon.hip, for the run of csrc/inr_optim.hip: the hyper-parameter check of mrirt_muon_step
+int muon_check_hp(const MrirtMuon* hp);
+
 }  // namespace mrirt

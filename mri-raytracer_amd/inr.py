@@ -749,14 +749,25 @@ def train_cfg(micro_batch: int, accum: int, seed: int, class_weights, dice_weigh
     return c
 
 
-def train_run(desc: _lib.InrDesc, cache: VoxelCache, cfg: _lib.InrTrainCfg, st: AdamWState, steps: int, scratch: Optional[torch.Tensor] = None):
+def _run_entry(desc: _lib.InrDesc, muon: Optional[_lib.Muon]):
+    """(name, scratch-size function, run function taking (desc, cache, cfg, state, ...)) of the one-call run for ``desc``."""
+    lib = _lib.lib()
+    if muon is not None:
+        run = lib.mrirt_inr_train_run_muon
+        return "mrirt_inr_train_run_muon", lib.mrirt_inr_train_run_muon_scratch_bytes, lambda d, c, g, *rest: run(d, c, g, C.byref(muon), *rest)
+    family = "siren" if int(desc.kind) in (KIND_SIREN, KIND_RAW_SIREN) else "inr"
+    return f"mrirt_{family}_train_run", getattr(lib, f"mrirt_{family}_train_run_scratch_bytes"), getattr(lib, f"mrirt_{family}_train_run")
+
+
+def train_run(desc: _lib.InrDesc, cache: VoxelCache, cfg: _lib.InrTrainCfg, st: AdamWState, steps: int, scratch: Optional[torch.Tensor] = None,
+              muon: Optional[_lib.Muon] = None):
     """``mrirt_inr_train_run`` (``mrirt_siren_train_run`` for a SIREN descriptor): ``steps`` optimiser steps from ``st.step``
     on, enqueued in one call without a host
     synchronisation.  Returns the device tensor history (steps, accum, 1 + 2 C): loss, CE per class, Dice per class of every
-    micro-batch.  ``st`` is updated in place and ``st.step`` advanced."""
-    lib = _lib.lib()
-    family = "siren" if int(desc.kind) in (KIND_SIREN, KIND_RAW_SIREN) else "inr"
-    run_bytes, run = getattr(lib, f"mrirt_{family}_train_run_scratch_bytes"), getattr(lib, f"mrirt_{family}_train_run")
+    micro-batch.  ``st`` is updated in place and ``st.step`` advanced.  ``muon`` (``muon_hp(...)``): the update is Muon on the
+    weight matrices and AdamW on the biases (``mrirt_inr_train_run_muon``); ``cfg.adamw`` then is the bias / clip half and
+    ``st.nu_w`` is left alone."""
+    where, run_bytes, run = _run_entry(desc, muon)
     nbytes = int(run_bytes(C.byref(desc), C.byref(cache.desc), C.byref(cfg)))
     if nbytes <= 0:
         raise ValueError("train_run: unsupported network / cache / configuration (Fourier ReLU or SIREN kind over the cache's modalities, "
@@ -767,9 +778,74 @@ def train_run(desc: _lib.InrDesc, cache: VoxelCache, cfg: _lib.InrTrainCfg, st: 
     cs = st.c_state()
     rc = run(C.byref(desc), C.byref(cache.desc), C.byref(cfg), C.byref(cs), int(st.step), int(steps), _ptr(hist),
              _ptr(scratch), scratch.numel(), _stream_ptr(None))
-    _lib.check(rc, f"mrirt_{family}_train_run")
+    _lib.check(rc, where)
     st.step += int(steps)
     return hist
+
+
+# --- Muon (csrc/inr_muon.hip): optax.contrib.muon's defaults ----------------------------------------------
+MUON_BETA, MUON_NESTEROV, MUON_NS_STEPS, MUON_NS_COEFFS, MUON_EPS, MUON_WEIGHT_DECAY = 0.95, True, 5, (3.4445, -4.7750, 2.0315), 1e-8, 0.0
+MUON_BIAS_B1, MUON_BIAS_B2, MUON_BIAS_EPS, MUON_BIAS_WEIGHT_DECAY = 0.9, 0.999, 1e-8, 0.0      # the AdamW half, on the biases
+
+
+def muon_hp(beta: float = MUON_BETA, nesterov: bool = MUON_NESTEROV, ns_steps: int = MUON_NS_STEPS, ns_coeffs=MUON_NS_COEFFS, eps: float = MUON_EPS,
+            weight_decay: float = MUON_WEIGHT_DECAY) -> _lib.Muon:
+    c = [float(v) for v in ns_coeffs]
+    if len(c) != 3:
+        raise ValueError("ns_coeffs: three Newton-Schulz coefficients")
+    return _lib.Muon(float(beta), float(eps), float(weight_decay), (C.c_float * 3)(*c), int(ns_steps), 1 if nesterov else 0)
+
+
+def _muon_scratch(desc: _lib.InrDesc, dev) -> torch.Tensor:
+    nbytes = int(_lib.lib().mrirt_muon_scratch_bytes(C.byref(desc)))
+    if nbytes <= 0:
+        raise ValueError(f"unsupported network shape for Muon: in {desc.inDim}, hidden {desc.hidden} x {desc.numLayers - 1}, out {desc.outDim}")
+    return torch.empty(nbytes, dtype=torch.uint8, device=dev)
+
+
+def muon_orthogonalize(dims: Sequence[int], m_flat: torch.Tensor, hp: Optional[_lib.Muon] = None, scratch: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``mrirt_muon_orthogonalize``: Newton-Schulz of every layer's matrix of the network ``dims = [in, hidden, .., out]``, from
+    the flat fp32 weight layout (``AdamWState.w``'s) into a new tensor of the same layout, in one call."""
+    desc = train_desc(dims)
+    hp = hp if hp is not None else muon_hp()
+    m = m_flat.contiguous()
+    nw = sum(a * b for a, b in zip(dims[:-1], dims[1:]))
+    if m.dtype != torch.float32 or m.numel() != nw or not m.is_cuda:
+        raise ValueError(f"m_flat: {nw} float32 elements on the GPU")
+    if scratch is None:
+        scratch = _muon_scratch(desc, m.device)
+    out = torch.empty_like(m)
+    rc = _lib.lib().mrirt_muon_orthogonalize(C.byref(desc), _ptr(m), _ptr(out), C.byref(hp), _ptr(scratch), scratch.numel(), _stream_ptr(None))
+    _lib.check(rc, "mrirt_muon_orthogonalize")
+    return out
+
+
+def muon_step(st: AdamWState, gw: torch.Tensor, gb: torch.Tensor, lr: float, gscale: float = 1.0, clip_norm: float = 0.0,
+              hp: Optional[_lib.Muon] = None, b1: float = MUON_BIAS_B1, b2: float = MUON_BIAS_B2, eps: float = MUON_BIAS_EPS,
+              weight_decay: float = MUON_BIAS_WEIGHT_DECAY) -> torch.Tensor:
+    """``mrirt_muon_step`` in place on ``st`` (update number ``st.step + 1``; ``st.step`` is advanced): clip by the global norm
+    of ``gscale`` x (gw, gb), Muon (``hp``, default ``muon_hp()``) on the weight matrices of ``st.dims``, AdamW (b1, b2, eps,
+    weight_decay) on the biases.  ``st.nu_w`` is not touched.  Returns the fp64 device tensor [norm, clip factor]."""
+    desc = train_desc(st.dims)
+    hp = hp if hp is not None else muon_hp()
+    scratch = _muon_scratch(desc, st.w.device)
+    gnorm = torch.empty(2, dtype=torch.float64, device=st.w.device)
+    adamw = _lib.AdamW(lr, b1, b2, eps, weight_decay, clip_norm)
+    rc = _lib.lib().mrirt_muon_step(C.byref(desc), _ptr(st.w), _ptr(st.b), _ptr(gw), _ptr(gb), _ptr(st.mu_w), _ptr(st.mu_b), _ptr(st.nu_b),
+                                    C.byref(hp), C.byref(adamw), int(st.step), float(gscale), _ptr(gnorm), _ptr(scratch), scratch.numel(),
+                                    _stream_ptr(None))
+    _lib.check(rc, "mrirt_muon_step")
+    st.step += 1
+    return gnorm
+
+
+def _optimizer_of(config: Dict[str, Any]) -> Optional[_lib.Muon]:
+    """train.py:36: ``OPTIMIZER_CHOICE == "muon"`` picks Muon (optional MUON_BETA, MUON_NS_STEPS, MUON_NESTEROV,
+    MUON_WEIGHT_DECAY); any other value, or none, is AdamW, as in the reference's else-branch."""
+    if config.get("OPTIMIZER_CHOICE") != "muon":
+        return None
+    return muon_hp(beta=float(config.get("MUON_BETA", MUON_BETA)), nesterov=bool(config.get("MUON_NESTEROV", MUON_NESTEROV)),
+                   ns_steps=int(config.get("MUON_NS_STEPS", MUON_NS_STEPS)), weight_decay=float(config.get("MUON_WEIGHT_DECAY", MUON_WEIGHT_DECAY)))
 
 
 def _load_resume(path) -> Tuple[List[Dict[str, np.ndarray]], Optional[Dict[str, np.ndarray]]]:
@@ -809,13 +885,18 @@ def _train_loop(config: Dict[str, Any], cases_or_cache, val_cases, params, resum
     accum = (g + micro - 1) // micro
     decay_steps = max(1, train_steps - warmup)
     lr_schedule(float(config["LR"]), float(config["MIN_LR"]), warmup, decay_steps, 0)          # refuses T <= 0 before any work
+    muon = _optimizer_of(config)
+    name = "muon" if muon is not None else "adamw"
+    opt = None
+    if resume_from is not None:                          # read, and refused if it is the other optimiser's, before any GPU work
+        params, opt = _load_resume(resume_from)
+        saved = str(opt["optimizer"]) if opt is not None and "optimizer" in opt else "adamw"          # a file without the key is AdamW's
+        if opt is not None and saved != name:
+            raise ValueError(f"resume_from: the optimiser state beside the checkpoint is {saved}'s, the config asks for {name}")
     cache = cases_or_cache if isinstance(cases_or_cache, VoxelCache) else VoxelCache(cases_or_cache)
     val_cache = None if val_cases is None else (val_cases if isinstance(val_cases, VoxelCache) else VoxelCache(val_cases))
     in_dim = in_dim_of(cache)
-    opt = None
-    if resume_from is not None:
-        params, opt = _load_resume(resume_from)
-    elif params is None:
+    if resume_from is None and params is None:
         params = default_params(seed, in_dim, hidden_dims, nc)
     if isinstance(params, dict):                         # the SIREN notebook layout
         params = [{"W": W, "b": b} for W, b in _layers(params)]
@@ -827,21 +908,21 @@ def _train_loop(config: Dict[str, Any], cases_or_cache, val_cases, params, resum
             getattr(st, k).copy_(torch.from_numpy(np.asarray(opt[k], np.float32)))
         st.step = int(opt["step"])
     desc = make_desc(st.dims, cache)
+    bias_half = dict(b1=MUON_BIAS_B1, b2=MUON_BIAS_B2, eps=MUON_BIAS_EPS, weight_decay=MUON_BIAS_WEIGHT_DECAY) if muon is not None else {}
     cfg = train_cfg(micro, accum, seed, config["CLASS_WEIGHTS"], float(config["DICE_WEIGHT"]), float(config["LR"]), float(config["MIN_LR"]),
-                    warmup, decay_steps, float(config["CLIP_NORM"]))
+                    warmup, decay_steps, float(config["CLIP_NORM"]), **bias_half)
     if save_path is not None:
         save_path = pathlib.Path(save_path)
         save_path.mkdir(parents=True, exist_ok=True)
     loss_history: List[float] = []
     dice_history: List[List[float]] = [[] for _ in range(nc)]
     ce_history: List[List[float]] = [[] for _ in range(nc)]
-    family = "siren" if int(desc.kind) in (KIND_SIREN, KIND_RAW_SIREN) else "inr"
-    nbytes = int(getattr(_lib.lib(), f"mrirt_{family}_train_run_scratch_bytes")(C.byref(desc), C.byref(cache.desc), C.byref(cfg)))
+    nbytes = int(_run_entry(desc, muon)[1](C.byref(desc), C.byref(cache.desc), C.byref(cfg)))
     scratch = torch.empty(nbytes, dtype=torch.uint8, device=cache.device) if nbytes > 0 else None      # one buffer for every chunk
     while st.step < train_steps:
         first = st.step
         steps = min(train_steps, (first // every + 1) * every, first + 4096) - first
-        h = train_run(desc, cache, cfg, st, steps, scratch).cpu().numpy().astype(np.float64).mean(axis=1)     # per-step means
+        h = train_run(desc, cache, cfg, st, steps, scratch, muon).cpu().numpy().astype(np.float64).mean(axis=1)     # per-step means
         for k in range(steps):
             loss_history.append(float(h[k, 0]))
             for c in range(nc):
@@ -859,7 +940,7 @@ def _train_loop(config: Dict[str, Any], cases_or_cache, val_cases, params, resum
                 flat[f"W_{i}"], flat[f"b_{i}"] = layer["W"], layer["b"]
             ck = save_path / CHECKPOINT_BASENAME.format(step=st.step)
             np.savez_compressed(ck, **flat)
-            np.savez_compressed(ck.with_name(ck.stem + "_opt.npz"), step=np.int64(st.step),
+            np.savez_compressed(ck.with_name(ck.stem + "_opt.npz"), step=np.int64(st.step), **({"optimizer": np.str_("muon")} if muon is not None else {}),
                                 **{k: getattr(st, k).cpu().numpy() for k in ("mu_w", "mu_b", "nu_w", "nu_b")})
     state = {"train_cache": cache, "val_cache": val_cache, "vol_shape": cache.vol_shape, "loss_history": loss_history,
              "dice_history": dice_history, "ce_history": ce_history, "best_val_dice": None, "best_step": None, "save_path": save_path,
@@ -880,6 +961,10 @@ def train_inr(config: Dict[str, Any], cases_or_cache, val_cases=None, params=Non
     in ``checkpoint_step{step:06d}_opt.npz`` beside it.  ``resume_from``: such a file (with the moments beside it the run
     continues at its step and reproduces the uninterrupted run bit for bit; without them it restarts the schedule from the
     loaded parameters, as the reference does) or a ``model_load`` checkpoint.  ``log(step, metrics)`` is called per step.
+    ``OPTIMIZER_CHOICE == "muon"`` (train.py:36; the notebook's optimiser) replaces AdamW by Muon on the weight matrices with
+    AdamW on the biases, inside ``mrirt_inr_train_run_muon`` (optional MUON_BETA, MUON_NS_STEPS, MUON_NESTEROV,
+    MUON_WEIGHT_DECAY; optax's defaults otherwise); any other value keeps AdamW.  A Muon run's ``_opt.npz`` carries
+    ``optimizer = "muon"``; resuming a state with the other optimiser raises ``ValueError``.
     Returns ``(params, state)``: the reference's list of ``{"W", "b"}`` (NumPy) and a dict with ``loss_history``,
     ``dice_history`` / ``ce_history`` (per class), the caches, ``vol_shape`` and ``opt`` (the ``AdamWState``)."""
     K = int(config["FOURIER_FREQS"])
