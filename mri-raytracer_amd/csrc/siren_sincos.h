@@ -9,8 +9,9 @@
 // Taylor polynomials to r^17 / r^16 are then within 2^-58 of sin r / cos r (first dropped terms (pi/4)^19 / 19!,
 // (pi/4)^18 / 18!), i.e. the fp64 value carries < 2^-5 fp32 ulp of error before the single rounding: measured 0 differences
 // from float32(sin(float64(a))) on 2.2 M arguments, worst error 0.4999999 fp32 ulp.
-// Beyond the domain: a finite a is replaced by a * 0 (sin = +-0, cos = 1); NaN and +-inf give NaN for both, since a * 0 is
-// then NaN.  k is never converted to an integer: the quadrant is k - 4 rint(k / 4), compared as an fp64 value.
+// Beyond the domain: a finite a is replaced by a * 0 (sin = +0, cos = 1; +0 for a negative a too, and for a = -0, since then
+// r = -0 - (-0 * P1) = +0); NaN and +-inf give NaN for both, since a * 0 is then NaN.  k is never converted to an integer: the
+// quadrant is k - 4 rint(k / 4), compared as an fp64 value.
 #pragma once
 #include "mrirt_device.h"
 

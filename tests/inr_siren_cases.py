@@ -5,6 +5,11 @@ term, so the fp32 NumPy restatement (inr_siren_ref.np_step) is what a k-ordered 
 tests/test_inr_siren_ref.py proves the single term, the absence of denormal sines and the domain for each case.  dlogits is
 non-zero in one row p* (the block and slab edges of n = 321); a quarter of the cases accumulate into non-zero gradients.
 
+Further exact tiers, all selection nets against the same restatement: HEAD_COVER (n = 65; per width the heads lie over every
+hidden unit once), BEYOND_NET (rows beyond the sine's domain and at +-3e38, p* on one of them; the same net with a NaN and an
+inf input, forward only) and BATCH (inr_train_cases.BATCH_NS = 16383 .. 131073 points; dlogits non-zero in one row PER SLAB, so
+the fixed-order sum over the slabs adds up to 64 non-zero partials: the reference is inr_siren_ref.np_step_slabs).
+
 Tolerance cases (E2E): random siren_init nets.  ``E2E_TOL[name]`` is 8 x the worst deviation of the same step evaluated in fp32
 on the CPU (torch, the restated sine) from the fp64 step over five batch orders — |g32 - g64| / A for the gradients, relative
 to the largest fp64 magnitude for logits, loss, aux and dlogits (rule of DESIGN.md sections 13 / 14).  No point is removed: the
@@ -58,16 +63,14 @@ def exact_id(c):
                                                c["w0"], c["pstar"], "_acc" if c["acc"] else "", "_span" if c["span"] else "")
 
 
-@functools.lru_cache(maxsize=None)
-def exact_case(i):
-    """dict(net, layers, dims, x, coords, feats (as the kind takes them), dlogits, init_w, init_b, ref = np_step)."""
-    c = EXACT[i]
-    rng = np.random.default_rng(EXACT_SEED + i)
+def _selection_case(c, seed, n, make_x=None):
+    """A selection net of the dict ``c`` (ind, hidden, layers, out, kind, w0, pstar, acc, span, shift) on n points."""
+    rng = np.random.default_rng(seed)
     dims = [c["ind"]] + [c["hidden"]] * (c["layers"] - 1) + [c["out"]]
     layers = sr.selection_net(rng, dims, c["shift"])
     lim = 2.0 ** 20 - 16.0 if c["span"] else 2.0
-    x = rng.uniform(-lim, lim, (N, c["ind"])).astype(np.float32)
-    dl = np.zeros((N, c["out"]), np.float32)
+    x = rng.uniform(-lim, lim, (n, c["ind"])).astype(np.float32) if make_x is None else make_x(rng)
+    dl = np.zeros((n, c["out"]), np.float32)
     dl[c["pstar"]] = rng.standard_normal(c["out"]).astype(np.float32) + np.float32(3.0)          # no zero among them
     nw, nb = sum(a * b for a, b in zip(dims[:-1], dims[1:])), sum(dims[1:])
     init_w = rng.standard_normal(nw).astype(np.float32) if c["acc"] else None
@@ -76,6 +79,121 @@ def exact_case(i):
     return dict(net=c, layers=layers, dims=dims, x=x, coords=None if raw else np.ascontiguousarray(x[:, :3]),
                 feats=x if raw else np.ascontiguousarray(x[:, 3:]), dlogits=dl, init_w=init_w, init_b=init_b,
                 ref=sr.np_step(layers, x, c["w0"], dl, init_w, init_b))
+
+
+@functools.lru_cache(maxsize=None)
+def exact_case(i):
+    """dict(net, layers, dims, x, coords, feats (as the kind takes them), dlogits, init_w, init_b, ref = np_step)."""
+    return _selection_case(EXACT[i], EXACT_SEED + i, N)
+
+
+# ---- every hidden unit under a head: per width, out = 16 and the head's shift in steps of 16 -------------------------------------
+HEAD_N = 65                        # one 64-row block + 1 row, one slab
+HEAD_SEED = 8200
+
+
+def _head_cover_nets():
+    nets = []
+    for hid in HIDDENS:
+        for shift in range(0, hid, 16):
+            i = len(nets)
+            nets.append(dict(ind=17, hidden=hid, layers=3, out=16, kind=KIND_RAW_SIREN, w0=1.0 if i % 2 == 0 else 30.0, pstar=(0, 63, 64)[i % 3],
+                             acc=False, span=False, shift=shift))
+    return nets
+
+
+HEAD_COVER = _head_cover_nets()
+
+
+@functools.lru_cache(maxsize=None)
+def head_cover_case(i):
+    return _selection_case(HEAD_COVER[i], HEAD_SEED + i, HEAD_N)
+
+
+# ---- beyond the sine's domain: a third of the rows inside +-2^20, a third in +-(2^20, 2^24], a third at +-3e38 ---------------------
+BEYOND_NET = dict(ind=17, hidden=64, layers=3, out=4, kind=KIND_RAW_SIREN, w0=1.0, pstar=256, acc=False, span=False, shift=0)
+BEYOND_SEED = 8300
+BEYOND_NAN_AT, BEYOND_INF_AT = (10, 3), (200, 5)         # (row, input) of the NaN and of the +inf of the forward-only case
+
+
+def beyond_class(n=N):
+    """Row p's class: 0 inside the domain, 1 beyond it within +-(2^20, 2^24], 2 at +-3e38."""
+    return np.arange(n) % 3
+
+
+def _beyond_x(rng):
+    ind = BEYOND_NET["ind"]
+    sign = rng.choice(np.array([-1.0, 1.0]), (N, ind))
+    inside = rng.uniform(-(2.0 ** 20 - 16.0), 2.0 ** 20 - 16.0, (N, ind))
+    beyond = sign * rng.uniform(2.0 ** 20 + 16.0, 2.0 ** 24, (N, ind))            # a bias moves it by less than 16
+    cls = beyond_class()[:, None]
+    return np.where(cls == 0, inside, np.where(cls == 1, beyond, sign * 3e38)).astype(np.float32)
+
+
+@functools.lru_cache(maxsize=None)
+def beyond_case():
+    """The exact case whose p* lies on a row beyond the domain (class 1): sin = +0, cos = 1 there, the gradient passes through."""
+    assert beyond_class()[BEYOND_NET["pstar"]] == 1
+    return _selection_case(BEYOND_NET, BEYOND_SEED, N, _beyond_x)
+
+
+@functools.lru_cache(maxsize=None)
+def nonfinite_case():
+    """The forward of beyond_case's net with one NaN and one +inf input element in two rows: dict(x, rows, logits, ins, cos)."""
+    e = beyond_case()
+    x = e["x"].copy()
+    x[BEYOND_NAN_AT], x[BEYOND_INF_AT] = np.nan, np.inf
+    logits, ins, cs = sr.np_forward(e["layers"], x, BEYOND_NET["w0"])
+    return dict(x=x, rows=(BEYOND_NAN_AT[0], BEYOND_INF_AT[0]), logits=logits, ins=ins, cos=cs)
+
+
+# ---- batch sweep: selection nets on both sides of every doubling of the slab length (inr_train_cases.BATCH_NS) ---------------------
+# (kind, in, hidden, layers, out, w0, n, accumulate).  dlogits has ONE non-zero row per slab -- the slab's first, last or middle
+# point for z mod 3 = 0, 1, 2 -- so every slab's partial has one non-zero term and the fixed-order sum over the slabs adds up to
+# 64 non-zero partials: inr_siren_ref.np_step_slabs is what the kernels must give bit for bit.
+BATCH = ([(KIND_SIREN, 7, 32, 2, 4, 30.0, n, n == 65537) for n in tc.BATCH_NS] +
+         [(KIND_RAW_SIREN, 31, 64, 3, 4, 1.0, n, False) for n in tc.BATCH_NS if n <= 32769] +
+         [(KIND_SIREN, 7, 256, 3, 4, 30.0, 65537, False)])
+BATCH_SEED = 8400
+BATCH_REPEAT = (KIND_SIREN, 7, 32, 2, 4, 30.0, 131073, False)      # this case runs its step twice: the same bytes
+GUARD_NS = (16385, 65537)                                         # the raw-ABI cases: net 7 -> 32 -> 4 of BATCH at these n
+RUN_LONG_MICRO = lc.RUN_LONG_MICRO
+
+
+def batch_id(c):
+    return "%s_in%d_h%d_L%d_o%d_w%g_n%d%s" % ("siren" if c[0] == KIND_SIREN else "raw", *c[1:7], "_acc" if c[7] else "")
+
+
+def batch_index(ind, hidden, n):
+    return next(i for i, c in enumerate(BATCH) if c[1] == ind and c[2] == hidden and c[6] == n)
+
+
+def slab_rows(n):
+    """The one row per slab that carries a non-zero dlogits."""
+    rows = []
+    for z, (k0, k1) in enumerate(sr.slab_ranges(n)):
+        rows.append((k0, k1 - 1, k0 + (k1 - k0) // 2)[z % 3])
+    return np.array(rows)
+
+
+@functools.lru_cache(maxsize=None)
+def batch_case(i):
+    """dict(net tuple, layers, dims, x, coords, feats, dlogits, rows, init_w, init_b, w0, ref = np_step_slabs)."""
+    kind, ind, hid, depth, out, w0, n, acc = BATCH[i]
+    rng = np.random.default_rng(BATCH_SEED + i)
+    dims = [ind] + [hid] * (depth - 1) + [out]
+    layers = sr.selection_net(rng, dims)
+    x = rng.uniform(-2.0, 2.0, (n, ind)).astype(np.float32)
+    rows = slab_rows(n)
+    dl = np.zeros((n, out), np.float32)
+    dl[rows] = rng.standard_normal((rows.size, out)).astype(np.float32) + np.float32(3.0)
+    nw, nb = sum(a * b for a, b in zip(dims[:-1], dims[1:])), sum(dims[1:])
+    init_w = rng.standard_normal(nw).astype(np.float32) if acc else None
+    init_b = rng.standard_normal(nb).astype(np.float32) if acc else None
+    raw = kind == KIND_RAW_SIREN
+    return dict(net=BATCH[i], layers=layers, dims=dims, x=x, coords=None if raw else np.ascontiguousarray(x[:, :3]),
+                feats=x if raw else np.ascontiguousarray(x[:, 3:]), dlogits=dl, rows=rows, init_w=init_w, init_b=init_b, w0=w0, n=n, kind=kind,
+                ref=sr.np_step_slabs(layers, x, w0, dl, sr.slab_len(n), init_w, init_b))
 
 
 # ---- tolerance tier ---------------------------------------------------------------------------------------------------------------
@@ -151,8 +269,8 @@ def run_layers():
     return sr.siren_layers(np.random.default_rng(RUN_INIT_SEED), run_dims(), W0)
 
 
-def run_cfg(accum):
-    return dict(lc.run_cfg(accum), w0=W0)
+def run_cfg(accum, micro=None):
+    return dict(lc.run_cfg(accum, micro), w0=W0)
 
 
 E2E_CONFIG = dict(GLOBAL_BATCH_SIZE=1024, MICRO_BATCH_SIZE=512, HIDDEN_DIMS=[32, 32], LR=3e-3, MIN_LR=1e-4, WARMUP_STEPS=4,

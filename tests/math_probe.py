@@ -83,6 +83,8 @@ def lib() -> C.CDLL:
         l.probe_fill_locate_args.argtypes = [vp, i64, vp]
         l.probe_fill_locate_args.restype = None
         l.probe_locate.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]
+        l.probe_siren_sincos.argtypes = [vp, vp, vp, i64, vp]
+        l.probe_siren_sincos.restype = i32
         for fn in ("probe_divu", "probe_exp", "probe_pow", "probe_clampf", "probe_clampf_k3", "probe_satf", "probe_lerp", "probe_lerp2", "probe_trilerp2",
                    "probe_primary_ray", "probe_store_rgba", "probe_wave_count", "probe_composite", "probe_locate"):
             getattr(l, fn).restype = i32
@@ -182,6 +184,15 @@ def pow_strict(x, y):
     out = torch.empty_like(tx)
     _run("probe_pow", lib().probe_pow(tx.data_ptr(), ty.data_ptr(), out.data_ptr(), tx.numel(), _stream()))
     return out.cpu().numpy()
+
+
+def siren_sincos(a):
+    """siren_sincos of csrc/siren_sincos.h, one thread per element: (sin, cos) as float32 arrays of a's size."""
+    import torch
+    ta = _dev(np.asarray(a, dtype=np.float32).reshape(-1))
+    s, c = torch.empty_like(ta), torch.empty_like(ta)
+    _run("probe_siren_sincos", lib().probe_siren_sincos(ta.data_ptr(), s.data_ptr(), c.data_ptr(), ta.numel(), _stream()))
+    return s.cpu().numpy(), c.cpu().numpy()
 
 
 def clampf(x, lo, hi):

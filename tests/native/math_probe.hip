@@ -1,4 +1,5 @@
-// TEST INFRASTRUCTURE: one entry point per device math primitive of csrc/mrirt_device.h / csrc/brats_device.h, so that
+// TEST INFRASTRUCTURE: one entry point per device math primitive of csrc/mrirt_device.h / csrc/brats_device.h and for the SIREN
+// step's siren_sincos (csrc/siren_sincos.h, against tests/inr_siren_ref.py's restatement), so that
 // tests/test_gpu_math_primitives.py can run each function ON ITS OWN over chosen arguments and compare it with the exact
 // references of tests/math_ref.py.  Built by tests/math_probe.py into tests/native/_build/libmrirt_probe.so with the
 // product's own compiler flags (mrirt._lib.HIPCC_FLAGS: -O3 -ffp-contract=off are what the STRICT contract rests on); the
@@ -8,6 +9,7 @@
 // threads and returns hipGetLastError().  The host entries (probe_make_udiv, probe_fill_exp_consts, probe_fill_camera,
 // probe_fill_k1args, probe_sizeof) run the product's host-side helpers and need no GPU.
 #include "../../mri-raytracer_amd/csrc/brats_device.h"
+#include "../../mri-raytracer_amd/csrc/siren_sincos.h"
 
 namespace mrirt { thread_local int g_last_hip_error = 0; }      // declared by mrirt_host.h, defined in libmrirt.so only
 
@@ -69,6 +71,16 @@ __global__ void __launch_bounds__(kThreads) clamp_k3_kernel(const float* __restr
 }
 __global__ void __launch_bounds__(kThreads) sat_kernel(const float* __restrict__ x, float* __restrict__ out, int64_t n) {
     PROBE_LOOP(i, n) out[i] = satf(x[i]);
+}
+
+// ---- the SIREN step's sine and cosine (csrc/siren_sincos.h) ----------------------------------------------------------
+__global__ void __launch_bounds__(kThreads) siren_sincos_kernel(const float* __restrict__ a, float* __restrict__ sn,
+                                                                float* __restrict__ cs, int64_t n) {
+    PROBE_LOOP(i, n) {
+        float s, c;
+        siren_sincos(a[i], s, c);
+        sn[i] = s; cs[i] = c;
+    }
 }
 
 // ---- lerp, lerp2, trilerp2 ------------------------------------------------------------------------------------------
@@ -271,6 +283,14 @@ int probe_clampf_k3(const float* x, float* out, int64_t n, hipStream_t s) {
 int probe_satf(const float* x, float* out, int64_t n, hipStream_t s) {
     if (n <= 0) return 0;
     sat_kernel<<<grid_for(n), kThreads, 0, s>>>(x, out, n);
+    return launched();
+}
+// one thread per element: ceil(n / 256) blocks, no stride loop
+int probe_siren_sincos(const float* a, float* sn, float* cs, int64_t n, hipStream_t s) {
+    if (n <= 0) return 0;
+    const int64_t blocks = (n + kThreads - 1) / kThreads;
+    if (blocks > (int64_t)1 << 24) return -1;
+    siren_sincos_kernel<<<dim3((unsigned)blocks), kThreads, 0, s>>>(a, sn, cs, n);
     return launched();
 }
 int probe_lerp(int strict, const float* a, const float* b, const float* t, float* out, int64_t n, hipStream_t s) {

@@ -1,10 +1,11 @@
-"""The device math primitives of csrc/mrirt_device.h and csrc/brats_device.h, each run ON ITS OWN through the probe library
+"""The device math primitives of csrc/mrirt_device.h, csrc/brats_device.h and csrc/siren_sincos.h, each run ON ITS OWN through the probe library
 (tests/native/math_probe.hip, built with the product's flags) and compared bit for bit with the exact references of
 tests/math_ref.py on the case lists of tests/math_cases.py.  No assertion on a STRICT function has a tolerance.  The same
 assertion helpers are shown to fail on plausible wrong versions, without a GPU, in tests/test_math_ref_host.py."""
 import numpy as np
 import pytest
 
+import inr_siren_ref as sr
 import math_cases as cases
 import math_probe as probe
 import math_ref as R
@@ -102,6 +103,31 @@ def test_pow_with_exponent_one_returns_its_argument():
     x = cases.pow_identity_cases()
     got = probe.pow_strict(x, np.ones_like(x))
     assert np.array_equal(R.bits(got), R.bits(x)), x[R.bits(got) != R.bits(x)][:8]        # NaN payloads and signs included
+
+
+# ---- the SIREN step's sine and cosine ----------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", list(sr.SINCOS_SETS))
+def test_siren_sincos_has_the_bits_of_its_restatement(name):
+    """siren_sincos, one thread per argument, on the argument sets of inr_siren_ref.py: the sweep of the CPU test, every fp32 of
+    [2^19, 2^20] in both signs, every quadrant switch of the domain with two neighbours on each side, +-0 / denormals / powers
+    of two / the domain's edge, and beyond the domain with infinities and NaNs.  Sine and cosine have the BIT PATTERNS of the
+    NumPy restatement (the sign of zero included; NaN exactly where it has one) and, inside the domain, the by-value figures
+    of the CPU test hold for the device's own results."""
+    a, want_s, want_c = sr.sincos_set(name)
+    s, c = probe.siren_sincos(a)
+    if name in sr.INSIDE_SETS:
+        sr.assert_libm_figures(name, "device", a, s, c)
+    for what, got, want in (("sin", s, want_s), ("cos", c, want_c)):
+        bad = sr.bits_differ(got, want)
+        print(f"device {name} {what}: {bad.size} of {a.size} bit patterns differ from the restatement")
+        assert bad.size == 0, (what, bad[:6], a[bad[:6]], got[bad[:6]], want[bad[:6]])
+    if name == "outside":
+        fin = np.isfinite(a)
+        assert (s[fin].view(np.uint32) == 0).all() and (c[fin] == 1).all() and np.isnan(s[~fin]).all() and np.isnan(c[~fin]).all()
+    if name == "small_and_special":
+        den = (np.abs(a) < F(2.0 ** -126)) & (a != 0)
+        assert den.sum() > 4000 and np.array_equal(s[den].view(np.uint32), a[den].view(np.uint32))         # denormals pass through
+        assert (s[a == 0].view(np.uint32) == 0).all()                                                    # sin(-0) = +0
 
 
 # ---- clamp ------------------------------------------------------------------------------------------------------------

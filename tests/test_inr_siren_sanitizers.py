@@ -52,6 +52,10 @@ def test_siren_step_and_sine_under_asan_and_ubsan():
     shapes += [(7, 32, 3, 4, cases.N, 0, 1), (65, 32, 2, 1, cases.N, 1, 1)]
     shapes += [(ind, hid, nh + 1, nc, n, int(kind == raw), 0) for kind, ind, hid, nh, nc, n in cases.E2E.values()]
     shapes += [(7, 256, 5, 4, 4096, 0, 0), (7, 32, 2, 4, 16385, 0, 0)]
+    # the batch sweep's (shape, n) pairs, the head-coverage shapes and the beyond-the-domain net: addresses only
+    shapes += [s for s in ((ind, hid, depth, out, n, int(kind == raw), 0) for kind, ind, hid, depth, out, _, n, _ in cases.BATCH) if s not in shapes]
+    shapes += sorted({(c["ind"], c["hidden"], c["layers"], c["out"], cases.HEAD_N, 1, 0) for c in cases.HEAD_COVER})
+    shapes += [(17, 64, 3, 4, cases.N, 1, 0)]
     args = [str(v) for s in shapes for v in s]
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
     r = subprocess.run([str(exe), *args], capture_output=True, text=True, env=env, timeout=900)
