@@ -38,7 +38,11 @@ extern "C" {
  *    SIREN training (no new struct): mrirt_siren_train_scratch_bytes, mrirt_siren_forward_f32, mrirt_siren_backward,
  *    mrirt_siren_train_run_scratch_bytes, mrirt_siren_train_run;
  *    Muon: MrirtMuon (mrirt_sizeof(11)), mrirt_muon_scratch_bytes, mrirt_muon_orthogonalize, mrirt_muon_step,
- *    mrirt_inr_train_run_muon_scratch_bytes, mrirt_inr_train_run_muon. */
+ *    mrirt_inr_train_run_muon_scratch_bytes, mrirt_inr_train_run_muon;
+ *    the extended loss and the tumour-ratio sampler: MrirtInrLossExt, MrirtInrTumourIndex, MrirtInrTrainExt
+ *    (mrirt_sizeof(13..15)), mrirt_inr_loss_ext_scratch_bytes, mrirt_inr_loss_ext, mrirt_inr_tumour_count,
+ *    mrirt_inr_tumour_index_scratch_bytes, mrirt_inr_tumour_index, mrirt_inr_sample_batch_mix,
+ *    mrirt_inr_train_run_ext_scratch_bytes, mrirt_inr_train_run_ext. */
 #define MRIRT_ABI_VERSION 4
 
 typedef enum MrirtStatus {
@@ -595,6 +599,96 @@ int mrirt_inr_train_run_muon(const MrirtInrDesc* desc, const MrirtInrCache* cach
                              int64_t scratch_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------ */
+/* The loss and the sampling mix of scripts/jax_inr_brats.py (lines 179-257, 466-528).    */
+/* Added within ABI 4: new symbols and three new structs only, mrirt_sizeof(13..15)      */
+/* ------------------------------------------------------------------------------------ */
+/* loss_fn of jax_inr_brats.py:205-257 on given logits.  C classes, n points, e = edemaClass, eps = labelSmoothing; per point
+ * yh_k = [label == k] (all 0 for a label outside 0..C-1), y_k = yh_k (1 - eps) + eps / C, p = softmax(z),
+ * ce_p = -sum_k y_k log p_k, w_p = classWeights[label] (0 for a label outside the range).
+ *   CE    focalGamma == 0: (1/n) sum_p ce_p w_p.  Otherwise pt = sum_k y_k p_k, m_p = max(1 - pt, 0)^gamma (times
+ *         sum_k y_k focalAlpha_k with flags bit 1) and CE = [(1/n) sum_p m_p ce_p] [(1/n) sum_p w_p].  The product of two means
+ *         is the reference's: focal_ce_loss returns a scalar, which lines 230-233 multiply by the weight vector and average.
+ *         (The clamp at 0 only acts where rounding puts pt above 1, where the reference's power is NaN.)
+ *   DL    I_k = sum_p p_k y_k, S_k = sum_p p_k + sum_p y_k, dice_k = (2 I_k + 1e-6) / (S_k + 1e-6); flags bit 0: 1 - mean_k dice_k
+ *         (model.py); clear: 1 - sum_k dice_k v_k, v_k = Y_k / (sum_j Y_j + 1e-6), Y_k = sum_p y_k (the script's default).
+ *   loss  = diceWeight > 0 ? (1 - dw) CE + dw DL : CE, then with g = [label == e], q = p_e, TP = sum q g, FP = sum q (1 - g),
+ *         FN = sum (1 - q) g, each only when its weight is > 0:
+ *           + edemaFpWeight FP / n  + tverskyWeight (1 - TP / (TP + tverskyAlpha FP + tverskyBeta FN + 1e-6))
+ *           + edemaLogitReg (1/n) sum_p softplus(z_e) (1 - g),  softplus(z) = max(z, 0) + log1p(exp(-|z|)).
+ * aux[2 C]: sum_p ce_p yh_k / max(count_k, 1), then dice_k.  terms[5] (may be NULL): CE, DL (0 when dw <= 0), FP / n, the
+ * Tversky index, the logit-regulariser mean (the last three 0 when e >= C).  dlogits[n][C] (may be NULL): the exact derivative
+ * of loss through the softmax Jacobian, the softplus' direct term added at j = e; y, v_k and the class-weight mean are
+ * constants.  Per-point values are fp32, every sum over the batch is fp64 in a fixed order (per-block partial sums, at most
+ * 256 blocks, added in block order): no float atomics, the same inputs give the same bits; no label indexes memory; three
+ * launches; no host synchronisation; loss, aux and terms stay on the device.  Finite logits give finite outputs.
+ * With focalGamma 0, labelSmoothing 0, flags bit 0 set and the three edema weights 0 it runs mrirt_inr_loss's operations in
+ * mrirt_inr_loss's order: the same bits in loss, aux and dlogits.
+ * Checks before any launch: MRIRT_ERR_NULL (logits, labels, ext, loss, aux, scratch); MRIRT_ERR_ARG for n outside 1..2^31-1,
+ * num_classes outside 1..16, focalGamma other than 0 or a value in [1, 8], labelSmoothing outside [0, 1), a non-finite
+ * diceWeight / class weight / focalAlpha (when used), a negative or non-finite edemaFpWeight, tverskyAlpha, tverskyBeta,
+ * tverskyWeight or edemaLogitReg, edemaClass >= num_classes while any of edemaFpWeight, tverskyWeight, edemaLogitReg is > 0,
+ * flags above 3, a scratch that is not 16-byte aligned or smaller than mrirt_inr_loss_ext_scratch_bytes(n). */
+typedef struct MrirtInrLossExt {
+    float classWeights[16];      /* first C read */
+    float focalAlpha[16];        /* read only with flags bit 1 */
+    float diceWeight;
+    float focalGamma;            /* 0: plain CE; otherwise 1 <= gamma <= 8 */
+    float labelSmoothing;        /* 0 <= eps < 1 */
+    float edemaFpWeight, tverskyAlpha, tverskyBeta, tverskyWeight, edemaLogitReg;   /* weights >= 0, finite */
+    uint32_t edemaClass;         /* the reference's 2; must be < C when any of the three edema weights is > 0 */
+    uint32_t flags;              /* bit 0: Dice = mean over classes (model.py); clear: prevalence-weighted (the script's default)
+                                    bit 1: focalAlpha is used */
+} MrirtInrLossExt;
+int64_t mrirt_inr_loss_ext_scratch_bytes(int64_t n);
+int mrirt_inr_loss_ext(const float* logits, const int32_t* labels, int64_t n, uint32_t num_classes, const MrirtInrLossExt* ext,
+                       float* loss, float* aux, float* terms, float* dlogits, void* scratch, int64_t scratch_bytes, void* stream);
+
+/* The tumour voxels of a cache: for every case the flat offsets (x W D + y D + z) of the voxels with seg > 0, ascending, the
+ * cases concatenated; offsets[c] .. offsets[c + 1] is case c's range.  Both arrays live on the device. */
+typedef struct MrirtInrTumourIndex {
+    const uint32_t* index;
+    const int64_t* offsets;      /* [ncases + 1] */
+} MrirtInrTumourIndex;
+/* counts[c] (device, [ncases]) = voxels of case c with seg > 0.  The caller reads them once (load time), forms the exclusive
+ * prefix sum offsets[ncases + 1] and sizes index by offsets[ncases].  mrirt_inr_tumour_index then fills index in ascending
+ * order: tumour voxels per chunk of 4096 voxels, a scan per case in a launch of its own, then the emit (three launches, no
+ * workgroup waits for another, no atomic append); a slot outside offsets[c] .. offsets[c + 1] is never written.  H W D >= 2^32
+ * is MRIRT_ERR_ARG; otherwise the cache's own limits hold.  scratch: device, 16-byte aligned,
+ * mrirt_inr_tumour_index_scratch_bytes(cache) bytes (0 for a refused cache). */
+int mrirt_inr_tumour_count(const MrirtInrCache* cache, int64_t* counts, void* stream);
+int64_t mrirt_inr_tumour_index_scratch_bytes(const MrirtInrCache* cache);
+int mrirt_inr_tumour_index(const MrirtInrCache* cache, const int64_t* offsets, uint32_t* index, void* scratch, int64_t scratch_bytes,
+                           void* stream);
+/* mrirt_inr_sample_batch with the first n_tumour points drawn from the tumour voxels (the reference puts its tumour draws
+ * first too, jax_inr_brats.py:466-528; its rejection loop and its one case per micro-batch are replaced by this rule, which
+ * is this library's: counter-based, one launch).  Point i >= n_tumour is mrirt_inr_sample_batch's point i, same bits.  Point
+ * i < n_tumour takes the same Philox words r0..r3: case = mulhi32(r0, ncases), cnt = offsets[case + 1] - offsets[case]; with
+ * cnt > 0 the voxel is index[offsets[case] + ((uint64) r1 cnt >> 32)], decoded to (x, y, z); with cnt == 0 the uniform draw
+ * from r1..r3 (the reference's "fallback fill").  0 <= n_tumour <= n, else MRIRT_ERR_ARG; n_tumour == 0 accepts a NULL
+ * index.  The host forms n_tumour = int(n clip(ratio, 0, 1)) in double, as line 468 does. */
+int mrirt_inr_sample_batch_mix(const MrirtInrCache* cache, const MrirtInrTumourIndex* tumour, uint64_t seed, uint64_t batch_index,
+                               int64_t n, int64_t n_tumour, float* coords, float* feats, int32_t* labels, void* stream);
+
+/* One run for every combination: the step by desc->kind (MRIRT_INR_FOURIER_RELU or MRIRT_INR_SIREN), the update Muon when
+ * muon is given (else AdamW), the loss mrirt_inr_loss_ext when loss is given (cfg->classWeights / diceWeight are then not
+ * read by the loss, though still checked), the sampler mrirt_inr_sample_batch_mix when nTumour > 0 (0 <= nTumour <=
+ * cfg->microBatch; tumour.index / .offsets then required).  With every member NULL / 0 it enqueues the launches of
+ * mrirt_inr_train_run / mrirt_siren_train_run and returns their bits.  The history layout is mrirt_inr_train_run's.
+ * scratch: the plain run's, then mrirt_muon_step's (with muon), then mrirt_inr_loss_ext's (with loss).  Every member is
+ * checked before anything is launched. */
+typedef struct MrirtInrTrainExt {
+    const MrirtInrLossExt* loss;
+    const MrirtMuon* muon;
+    MrirtInrTumourIndex tumour;
+    int64_t nTumour;
+} MrirtInrTrainExt;
+int64_t mrirt_inr_train_run_ext_scratch_bytes(const MrirtInrDesc* desc, const MrirtInrCache* cache, const MrirtInrTrainCfg* cfg,
+                                              const MrirtInrTrainExt* ext);
+int mrirt_inr_train_run_ext(const MrirtInrDesc* desc, const MrirtInrCache* cache, const MrirtInrTrainCfg* cfg,
+                            const MrirtInrTrainExt* ext, const MrirtInrTrainState* state, uint64_t first_step, uint32_t steps,
+                            float* history, void* scratch, int64_t scratch_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------ */
 /* Exact distance transform and Hausdorff distance (inr/inr/model.py:164-195)            */
 /* ------------------------------------------------------------------------------------ */
 /* labels / pred / truth: the int16 [H][W][D] C-order volume mrirt_inr_predict_volume writes (device).  The coordinate of
@@ -704,7 +798,8 @@ const char* mrirt_status_string(int status);
 int mrirt_last_hip_error(void);            /* hipError_t of the last failed HIP call on this thread */
 uint32_t mrirt_sizeof(uint32_t which);     /* 0 BratsParams, 1 RenderExt, 2 VolumeParams, 3 SdfParams, 4 InrDesc, 5 Skip,
                                               6 MeshParams, 7 InrCache, 8 AdamW, 9 InrTrainCfg, 10 InrTrainState,
-                                              11 Muon */
+                                              11 Muon, 13 InrLossExt, 14 InrTumourIndex, 15 InrTrainExt; 12 is
+                                              unassigned and stays 0, as every index beyond 15 */
 /* Opt-in diagnostics (host only; the library installs nothing by itself): a SIGABRT handler that writes the native
  * backtrace of the aborting thread and, when file descriptor 2 has been redirected into a regular file (a test runner's
  * capture), the tail of that file to `fd` — a descriptor the caller duplicated before the redirection — and then chains

@@ -17,7 +17,7 @@ CSRC = PKG_DIR / "csrc"
 INCLUDE = PKG_DIR.parent / "include"
 SO_PATH = pathlib.Path(os.environ.get("MRIRT_LIB", PKG_DIR / "libmrirt.so"))   # override: A/B builds in development
 HIP_SOURCES = ["brats_march.hip", "brats_skip.hip", "brats_c5.hip", "brats_slab.hip", "brats_ring.hip", "brats_backward.hip", "volume_march.hip", "grid_ops.hip", "inr_mlp.hip",
-               "inr_train.hip", "inr_optim.hip", "inr_muon.hip", "mesh_rt.hip", "edt.hip", "surface.hip", "abort_trace.cpp"]
+               "inr_train.hip", "inr_optim.hip", "inr_muon.hip", "inr_lossx.hip", "mesh_rt.hip", "edt.hip", "surface.hip", "abort_trace.cpp"]
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17", "-Wall"]
 
 # every extern "C" symbol include/mrirt.h declares
@@ -39,6 +39,8 @@ ABI_SYMBOLS = [
     "mrirt_siren_train_run_scratch_bytes", "mrirt_siren_train_run",
     "mrirt_muon_scratch_bytes", "mrirt_muon_orthogonalize", "mrirt_muon_step",
     "mrirt_inr_train_run_muon_scratch_bytes", "mrirt_inr_train_run_muon",
+    "mrirt_inr_loss_ext_scratch_bytes", "mrirt_inr_loss_ext", "mrirt_inr_tumour_count", "mrirt_inr_tumour_index_scratch_bytes",
+    "mrirt_inr_tumour_index", "mrirt_inr_sample_batch_mix", "mrirt_inr_train_run_ext_scratch_bytes", "mrirt_inr_train_run_ext",
 ]
 
 ABI_VERSION = 4          # MRIRT_ABI_VERSION of include/mrirt.h this binding was written against
@@ -142,6 +144,26 @@ class InrTrainState(C.Structure):
 class Muon(C.Structure):
     """MrirtMuon: the hyper-parameters of optax's scale_by_muon."""
     _fields_ = [("beta", f32), ("eps", f32), ("weightDecay", f32), ("nsCoeffs", f32 * 3), ("nsSteps", u32), ("nesterov", u32)]
+
+
+LOSS_PER_CLASS_DICE, LOSS_FOCAL_ALPHA = 1, 2          # MrirtInrLossExt.flags
+
+
+class InrLossExt(C.Structure):
+    """MrirtInrLossExt: the loss options of scripts/jax_inr_brats.py:205-257."""
+    _fields_ = [("classWeights", f32 * 16), ("focalAlpha", f32 * 16), ("diceWeight", f32), ("focalGamma", f32), ("labelSmoothing", f32),
+                ("edemaFpWeight", f32), ("tverskyAlpha", f32), ("tverskyBeta", f32), ("tverskyWeight", f32), ("edemaLogitReg", f32),
+                ("edemaClass", u32), ("flags", u32)]
+
+
+class InrTumourIndex(C.Structure):
+    """MrirtInrTumourIndex: device pointers to the ascending tumour voxel offsets and the per-case ranges."""
+    _fields_ = [("index", C.c_void_p), ("offsets", C.c_void_p)]
+
+
+class InrTrainExt(C.Structure):
+    """MrirtInrTrainExt: what mrirt_inr_train_run_ext takes beyond the plain run; every member may be NULL / 0."""
+    _fields_ = [("loss", C.POINTER(InrLossExt)), ("muon", C.POINTER(Muon)), ("tumour", InrTumourIndex), ("nTumour", C.c_int64)]
 
 
 class Skip(C.Structure):
@@ -392,6 +414,23 @@ def lib() -> C.CDLL:
     l.mrirt_inr_train_run_muon.argtypes = [C.POINTER(InrDesc), C.POINTER(InrCache), C.POINTER(InrTrainCfg), C.POINTER(Muon),
                                            C.POINTER(InrTrainState), u64, u32, vp, vp, i64, vp]
     l.mrirt_inr_train_run_muon.restype = i32
+    l.mrirt_inr_loss_ext_scratch_bytes.argtypes = [i64]
+    l.mrirt_inr_loss_ext_scratch_bytes.restype = i64
+    l.mrirt_inr_loss_ext.argtypes = [vp, vp, i64, u32, C.POINTER(InrLossExt), vp, vp, vp, vp, vp, i64, vp]
+    l.mrirt_inr_loss_ext.restype = i32
+    l.mrirt_inr_tumour_count.argtypes = [C.POINTER(InrCache), vp, vp]
+    l.mrirt_inr_tumour_count.restype = i32
+    l.mrirt_inr_tumour_index_scratch_bytes.argtypes = [C.POINTER(InrCache)]
+    l.mrirt_inr_tumour_index_scratch_bytes.restype = i64
+    l.mrirt_inr_tumour_index.argtypes = [C.POINTER(InrCache), vp, vp, vp, i64, vp]
+    l.mrirt_inr_tumour_index.restype = i32
+    l.mrirt_inr_sample_batch_mix.argtypes = [C.POINTER(InrCache), C.POINTER(InrTumourIndex), u64, u64, i64, i64, vp, vp, vp, vp]
+    l.mrirt_inr_sample_batch_mix.restype = i32
+    l.mrirt_inr_train_run_ext_scratch_bytes.argtypes = [C.POINTER(InrDesc), C.POINTER(InrCache), C.POINTER(InrTrainCfg), C.POINTER(InrTrainExt)]
+    l.mrirt_inr_train_run_ext_scratch_bytes.restype = i64
+    l.mrirt_inr_train_run_ext.argtypes = [C.POINTER(InrDesc), C.POINTER(InrCache), C.POINTER(InrTrainCfg), C.POINTER(InrTrainExt),
+                                          C.POINTER(InrTrainState), u64, u32, vp, vp, i64, vp]
+    l.mrirt_inr_train_run_ext.restype = i32
     l.mrirt_status_string.argtypes = [i32]
     l.mrirt_status_string.restype = C.c_char_p
     l.mrirt_sizeof.argtypes = [u32]
@@ -405,8 +444,8 @@ def lib() -> C.CDLL:
         raise ImportError(f"ABI mismatch: {SO_PATH} reports version {l.mrirt_abi_version()}, this binding expects {ABI_VERSION} "
                           "(rebuild: python -c \"import __graft_entry__ as g; g.build()\")")
     for which, st in enumerate((BratsParams, RenderExt, VolumeParams, SdfParams, InrDesc, Skip, MeshParams, InrCache, AdamW, InrTrainCfg,
-                                InrTrainState, Muon)):
-        if l.mrirt_sizeof(which) != C.sizeof(st):
+                                InrTrainState, Muon, None, InrLossExt, InrTumourIndex, InrTrainExt)):          # index 12 is unassigned
+        if st is not None and l.mrirt_sizeof(which) != C.sizeof(st):
             raise ImportError(f"ABI mismatch: {st.__name__} is {C.sizeof(st)} B here, {l.mrirt_sizeof(which)} B in {SO_PATH}")
     _LIB = l
     return l

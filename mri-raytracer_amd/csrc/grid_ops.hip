@@ -451,6 +451,9 @@ extern "C" uint32_t mrirt_sizeof(uint32_t which) {
         case 9: return (uint32_t)sizeof(MrirtInrTrainCfg);
         case 10: return (uint32_t)sizeof(MrirtInrTrainState);
         case 11: return (uint32_t)sizeof(MrirtMuon);
+        case 13: return (uint32_t)sizeof(MrirtInrLossExt);          // 12 stays unassigned (0): it was, and callers may rely on it
+        case 14: return (uint32_t)sizeof(MrirtInrTumourIndex);
+        case 15: return (uint32_t)sizeof(MrirtInrTrainExt);
         default: return 0;
     }
 }

@@ -189,6 +189,7 @@ static int launch_adamw(const OptArgs& a, hipStream_t s) {
 }
 
 int opt_check_adamw(const MrirtAdamW* hp, bool needLr) { return check_adamw(hp, needLr); }
+int opt_check_cache(const MrirtInrCache* cache) { return check_cache(cache); }
 
 int opt_norm_and_bias_step(const float* gw, int64_t nw, float* b, const float* gb, float* mu_b, float* nu_b, int64_t nb,
                            const MrirtAdamW* hp, uint64_t t, float gscale, double* gnorm, void* scratch, hipStream_t stream) {
@@ -292,11 +293,31 @@ extern "C" int64_t mrirt_siren_train_run_scratch_bytes(const MrirtInrDesc* desc,
     return run_scratch_bytes(desc, true, cache, cfg);
 }
 
+// mrirt_inr_train_run_ext's extras: the loss and the sampler of csrc/inr_lossx.hip.  All NULL / 0: the plain run.
+struct RunExtras {
+    const MrirtInrLossExt* loss;
+    MrirtInrTumourIndex tumour;
+    int64_t nTumour;
+};
+
+// what mrirt_inr_loss_ext / mrirt_inr_sample_batch_mix would refuse of the extras, before any launch
+static int check_extras(const RunExtras& x, const MrirtInrDesc* desc, const MrirtInrTrainCfg* cfg) {
+    if (x.loss) {
+        const int rc = lossx_check(x.loss, desc->outDim);
+        if (rc != MRIRT_OK) return rc;
+    }
+    if (x.nTumour < 0 || x.nTumour > cfg->microBatch) return MRIRT_ERR_ARG;
+    if (x.nTumour > 0 && (!x.tumour.index || !x.tumour.offsets)) return MRIRT_ERR_NULL;
+    return MRIRT_OK;
+}
+
 // One loop for both families: the kind picks the public forward / backward pair, everything else is shared.
 // muon: NULL for AdamW; else the update is mrirt_muon_step, whose scratch lies behind the AdamW run's.
+// extras: NULL for the plain run; else its loss (whose scratch lies behind Muon's) and / or its sampler replace the plain ones.
 static int train_run(const MrirtInrDesc* desc, bool siren, const MrirtInrCache* cache, const MrirtInrTrainCfg* cfg,
                      const MrirtInrTrainState* state, uint64_t first_step, uint32_t steps, float* history,
-                     void* scratch, int64_t scratch_bytes, void* stream, const MrirtMuon* muon = nullptr) {
+                     void* scratch, int64_t scratch_bytes, void* stream, const MrirtMuon* muon = nullptr,
+                     const RunExtras* extras = nullptr) {
     TrainLayout L;
     RunLayout R;
     if (!desc || !cache || !cfg || !state || !history) return MRIRT_ERR_NULL;
@@ -309,7 +330,11 @@ static int train_run(const MrirtInrDesc* desc, bool siren, const MrirtInrCache* 
         if ((rc = muon_check_hp(muon)) != MRIRT_OK) return rc;
         if (muonBytes <= 0) return MRIRT_ERR_ARG;
     }
-    if ((rc = check_opt_scratch(scratch, scratch_bytes, R.bytes + (uint64_t)muonBytes)) != MRIRT_OK) return rc;
+    if (extras && (rc = check_extras(*extras, desc, cfg)) != MRIRT_OK) return rc;
+    const MrirtInrLossExt* lossExt = extras ? extras->loss : nullptr;
+    const bool mix = extras && extras->nTumour > 0;
+    const int64_t lossBytes = lossExt ? mrirt_inr_loss_ext_scratch_bytes(cfg->microBatch) : 0;
+    if ((rc = check_opt_scratch(scratch, scratch_bytes, R.bytes + (uint64_t)muonBytes + (uint64_t)lossBytes)) != MRIRT_OK) return rc;
     const int64_t n = cfg->microBatch;
     const uint32_t C = desc->outDim;
     char* base = (char*)scratch;
@@ -327,10 +352,13 @@ static int train_run(const MrirtInrDesc* desc, bool siren, const MrirtInrCache* 
         const uint64_t t = first_step + k;
         for (uint32_t a = 0; a < cfg->accum; ++a) {
             float* h = history + ((uint64_t)k * cfg->accum + a) * (1u + 2u * C);
-            if ((rc = mrirt_inr_sample_batch(cache, cfg->seed, t * cfg->accum + a, n, coords, feats, labels, stream)) != MRIRT_OK) return rc;
+            if (mix) rc = mrirt_inr_sample_batch_mix(cache, &extras->tumour, cfg->seed, t * cfg->accum + a, n, extras->nTumour, coords, feats, labels, stream);
+            else rc = mrirt_inr_sample_batch(cache, cfg->seed, t * cfg->accum + a, n, coords, feats, labels, stream);
+            if (rc != MRIRT_OK) return rc;
             if ((rc = (siren ? mrirt_siren_forward_f32 : mrirt_inr_forward_f32)(desc, state->w, state->b, coords, feats, n, logits, base, (int64_t)R.stepBytes, stream)) != MRIRT_OK) return rc;
-            if ((rc = mrirt_inr_loss(logits, labels, n, C, cfg->classWeights, cfg->diceWeight, h, h + 1, dlogits, base,
-                                     (int64_t)R.stepBytes, stream)) != MRIRT_OK) return rc;
+            if (lossExt) rc = mrirt_inr_loss_ext(logits, labels, n, C, lossExt, h, h + 1, nullptr, dlogits, base + R.bytes + muonBytes, lossBytes, stream);
+            else rc = mrirt_inr_loss(logits, labels, n, C, cfg->classWeights, cfg->diceWeight, h, h + 1, dlogits, base, (int64_t)R.stepBytes, stream);
+            if (rc != MRIRT_OK) return rc;
             if ((rc = (siren ? mrirt_siren_backward : mrirt_inr_backward)(desc, state->w, n, dlogits, gw, gb, a ? 1u : 0u, base, (int64_t)R.stepBytes, stream)) != MRIRT_OK) return rc;
         }
         double lr;
@@ -364,4 +392,33 @@ extern "C" int mrirt_inr_train_run_muon(const MrirtInrDesc* desc, const MrirtInr
                                         void* scratch, int64_t scratch_bytes, void* stream) {
     if (!desc || !hp) return MRIRT_ERR_NULL;
     return train_run(desc, desc->kind == MRIRT_INR_SIREN, cache, cfg, state, first_step, steps, history, scratch, scratch_bytes, stream, hp);
+}
+
+static bool run_ext_kind(const MrirtInrDesc* desc, const MrirtInrTrainExt* ext, bool& siren, RunExtras& x) {
+    if (!desc || !ext) return false;
+    siren = desc->kind == MRIRT_INR_SIREN;
+    x.loss = ext->loss; x.tumour = ext->tumour; x.nTumour = ext->nTumour;
+    return true;
+}
+
+// the plain run's scratch, then mrirt_muon_step's (with muon), then mrirt_inr_loss_ext's (with loss)
+extern "C" int64_t mrirt_inr_train_run_ext_scratch_bytes(const MrirtInrDesc* desc, const MrirtInrCache* cache, const MrirtInrTrainCfg* cfg,
+                                                         const MrirtInrTrainExt* ext) {
+    bool siren;
+    RunExtras x;
+    if (!run_ext_kind(desc, ext, siren, x) || !cfg) return 0;
+    const int64_t run = run_scratch_bytes(desc, siren, cache, cfg);
+    if (run <= 0 || check_extras(x, desc, cfg) != MRIRT_OK) return 0;
+    const int64_t step = ext->muon ? mrirt_muon_scratch_bytes(desc) : 0, loss = ext->loss ? mrirt_inr_loss_ext_scratch_bytes(cfg->microBatch) : 0;
+    if ((ext->muon && (step <= 0 || muon_check_hp(ext->muon) != MRIRT_OK)) || (ext->loss && loss <= 0)) return 0;
+    return run + step + loss;
+}
+
+extern "C" int mrirt_inr_train_run_ext(const MrirtInrDesc* desc, const MrirtInrCache* cache, const MrirtInrTrainCfg* cfg,
+                                       const MrirtInrTrainExt* ext, const MrirtInrTrainState* state, uint64_t first_step, uint32_t steps,
+                                       float* history, void* scratch, int64_t scratch_bytes, void* stream) {
+    bool siren;
+    RunExtras x;
+    if (!run_ext_kind(desc, ext, siren, x)) return MRIRT_ERR_NULL;
+    return train_run(desc, siren, cache, cfg, state, first_step, steps, history, scratch, scratch_bytes, stream, ext->muon, &x);
 }

@@ -211,5 +211,9 @@ int opt_norm_and_bias_step(const float* gw, int64_t nw, float* b, const float* g
                            const MrirtAdamW* hp, uint64_t t, float gscale, double* gnorm, void* scratch, hipStream_t stream);
 // csrc/inr_muon.hip, for the run of csrc/inr_optim.hip: the hyper-parameter check of mrirt_muon_step
 int muon_check_hp(const MrirtMuon* hp);
+// csrc/inr_optim.hip, for the tumour index and the mixed sampler (csrc/inr_lossx.hip): the cache check of mrirt_inr_sample_batch
+int opt_check_cache(const MrirtInrCache* cache);
+// csrc/inr_lossx.hip, for the run of csrc/inr_optim.hip: what mrirt_inr_loss_ext refuses of its struct for C classes
+int lossx_check(const MrirtInrLossExt* ext, uint32_t C);
 
 }  // namespace mrirt

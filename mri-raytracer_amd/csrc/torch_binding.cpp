@@ -304,6 +304,42 @@ std::tuple<Tensor, Tensor, Tensor> inr_loss(const Tensor& logits, const Tensor& 
     return { loss, aux, dl };
 }
 
+// (loss [1], aux [2, C], terms [5], dlogits [n, C]) of scripts/jax_inr_brats.py's loss through mrirt_inr_loss_ext; focal_alpha
+// empty: flags bit 1 clear
+std::tuple<Tensor, Tensor, Tensor, Tensor> inr_loss_ext(const Tensor& logits, const Tensor& labels, at::ArrayRef<double> class_weights,
+                                                        at::ArrayRef<double> focal_alpha, double dice_weight, bool per_class_dice, double focal_gamma,
+                                                        double label_smoothing, double edema_fp_weight, double tversky_alpha, double tversky_beta,
+                                                        double tversky_weight, double edema_logit_reg, int64_t edema_class) {
+    const float* z = static_cast<const float*>(dev_ptr(logits, at::kFloat, "logits"));
+    const int32_t* lab = static_cast<const int32_t*>(dev_ptr(labels, at::kInt, "labels"));
+    TORCH_CHECK_VALUE(logits.dim() == 2 && logits.size(0) >= 1 && labels.numel() == logits.size(0), "logits must be [n, C] with n >= 1 and labels [n]");
+    const int64_t n = logits.size(0), nc = logits.size(1);
+    TORCH_CHECK_VALUE(nc >= 1 && nc <= 16 && (int64_t)class_weights.size() == nc, "1..16 classes, one class weight each");
+    TORCH_CHECK_VALUE(focal_alpha.empty() || (int64_t)focal_alpha.size() == nc, "focal_alpha: empty, or one value per class");
+    TORCH_CHECK_VALUE(edema_class >= 0 && edema_class <= 0xffffffffll, "edema_class must fit 32 bits");
+    MrirtInrLossExt x;
+    std::memset(&x, 0, sizeof x);
+    for (int64_t k = 0; k < nc; ++k) {
+        x.classWeights[k] = (float)class_weights[k];
+        if (!focal_alpha.empty()) x.focalAlpha[k] = (float)focal_alpha[k];
+    }
+    x.diceWeight = (float)dice_weight; x.focalGamma = (float)focal_gamma; x.labelSmoothing = (float)label_smoothing;
+    x.edemaFpWeight = (float)edema_fp_weight; x.tverskyAlpha = (float)tversky_alpha; x.tverskyBeta = (float)tversky_beta;
+    x.tverskyWeight = (float)tversky_weight; x.edemaLogitReg = (float)edema_logit_reg;
+    x.edemaClass = (uint32_t)edema_class;
+    x.flags = (per_class_dice ? 1u : 0u) | (focal_alpha.empty() ? 0u : 2u);
+    std::optional<at::Device> dev = logits.device();
+    same_device(dev, labels, "labels");
+    DeviceGuard guard(*dev);
+    const int64_t nbytes = mrirt_inr_loss_ext_scratch_bytes(n);
+    const auto f32 = at::TensorOptions().dtype(at::kFloat).device(*dev);
+    Tensor loss = at::empty({ 1 }, f32), aux = at::empty({ 2, nc }, f32), terms = at::empty({ 5 }, f32), dl = at::empty_like(logits);
+    Tensor scratch = at::empty({ nbytes }, at::TensorOptions().dtype(at::kByte).device(*dev));
+    check(mrirt_inr_loss_ext(z, lab, n, (uint32_t)nc, &x, loss.data_ptr<float>(), aux.data_ptr<float>(), terms.data_ptr<float>(), dl.data_ptr<float>(),
+                             scratch.data_ptr(), nbytes, current_stream()), "mrirt_inr_loss_ext");
+    return { loss, aux, terms, dl };
+}
+
 // (grad_w, grad_b) through mrirt_inr_backward from dlogits and the scratch inr_forward_f32 returned
 std::tuple<Tensor, Tensor> inr_backward(const Tensor& weights, const Tensor& dlogits, const Tensor& scratch, int64_t kind, int64_t num_layers,
                                         int64_t in_dim, int64_t out_dim, int64_t hidden, int64_t fourier_freqs, int64_t num_mods, int64_t n) {
@@ -348,6 +384,41 @@ std::tuple<Tensor, Tensor, Tensor> inr_sample_batch(const OptTensor& mods_table,
     check(mrirt_inr_sample_batch(&c, (uint64_t)seed, (uint64_t)batch_index, n, coords.data_ptr<float>(),
                                  num_mods > 0 ? feats.data_ptr<float>() : nullptr, labels.data_ptr<int32_t>(), current_stream()),
           "mrirt_inr_sample_batch");
+    return { coords, feats, labels };
+}
+
+// inr_sample_batch with the first n_tumour points drawn from the tumour index (mrirt_inr_sample_batch_mix): tumour_index the
+// uint32 voxel offsets held in an int32 tensor, tumour_offsets int64 [ncases + 1]; both may be absent when n_tumour == 0
+std::tuple<Tensor, Tensor, Tensor> inr_sample_batch_mix(const OptTensor& mods_table, const Tensor& seg_table, const OptTensor& tumour_index,
+                                                        const OptTensor& tumour_offsets, int64_t num_mods, int64_t h, int64_t w, int64_t d,
+                                                        int64_t seed, int64_t batch_index, int64_t n, int64_t n_tumour) {
+    const void* st = dev_ptr(seg_table, at::kLong, "seg_table");
+    const void* mt = dev_ptr(mods_table, at::kLong, "mods_table");
+    const void* ti = dev_ptr(tumour_index, at::kInt, "tumour_index");
+    const void* to = dev_ptr(tumour_offsets, at::kLong, "tumour_offsets");
+    TORCH_CHECK_VALUE(seg_table.numel() >= 1 && (num_mods <= 0 || (mods_table.has_value() && mods_table->numel() == seg_table.numel())),
+                      "seg_table must hold one address per case, and mods_table as many when num_mods > 0");
+    TORCH_CHECK_VALUE(num_mods >= 0 && h >= 0 && w >= 0 && d >= 0 && n >= 0 && n_tumour >= 0, "negative extent");
+    TORCH_CHECK_VALUE(n_tumour == 0 || (tumour_index.has_value() && tumour_offsets.has_value() && tumour_offsets->numel() == seg_table.numel() + 1),
+                      "n_tumour > 0 needs tumour_index and tumour_offsets [ncases + 1]");
+    std::optional<at::Device> dev = seg_table.device();
+    same_device(dev, mods_table, "mods_table");
+    same_device(dev, tumour_index, "tumour_index");
+    same_device(dev, tumour_offsets, "tumour_offsets");
+    DeviceGuard guard(*dev);
+    MrirtInrCache c;
+    std::memset(&c, 0, sizeof c);
+    c.mods = num_mods > 0 ? static_cast<const float* const*>(mt) : nullptr;
+    c.seg = static_cast<const int16_t* const*>(st);
+    c.ncases = (uint32_t)seg_table.numel(); c.numMods = (uint32_t)num_mods;
+    c.hwd[0] = (uint32_t)h; c.hwd[1] = (uint32_t)w; c.hwd[2] = (uint32_t)d;
+    const MrirtInrTumourIndex t = { static_cast<const uint32_t*>(ti), static_cast<const int64_t*>(to) };
+    const auto f32 = at::TensorOptions().dtype(at::kFloat).device(*dev);
+    Tensor coords = at::empty({ n, 3 }, f32), feats = at::empty({ n, num_mods }, f32);
+    Tensor labels = at::empty({ n }, at::TensorOptions().dtype(at::kInt).device(*dev));
+    check(mrirt_inr_sample_batch_mix(&c, n_tumour > 0 ? &t : nullptr, (uint64_t)seed, (uint64_t)batch_index, n, n_tumour, coords.data_ptr<float>(),
+                                     num_mods > 0 ? feats.data_ptr<float>() : nullptr, labels.data_ptr<int32_t>(), current_stream()),
+          "mrirt_inr_sample_batch_mix");
     return { coords, feats, labels };
 }
 
@@ -491,6 +562,11 @@ TORCH_LIBRARY(mrirt_native, m) {
     m.def("inr_forward_f32(Tensor weights, Tensor biases, int kind, int num_layers, int in_dim, int out_dim, int hidden, "
           "int fourier_freqs, int num_mods, Tensor? coords, Tensor? feats, int n) -> (Tensor, Tensor)");
     m.def("inr_loss(Tensor logits, Tensor labels, float[] class_weights, float dice_weight) -> (Tensor, Tensor, Tensor)");
+    m.def("inr_loss_ext(Tensor logits, Tensor labels, float[] class_weights, float[] focal_alpha, float dice_weight, bool per_class_dice, "
+          "float focal_gamma, float label_smoothing, float edema_fp_weight, float tversky_alpha, float tversky_beta, float tversky_weight, "
+          "float edema_logit_reg, int edema_class) -> (Tensor, Tensor, Tensor, Tensor)");
+    m.def("inr_sample_batch_mix(Tensor? mods_table, Tensor seg_table, Tensor? tumour_index, Tensor? tumour_offsets, int num_mods, int h, int w, "
+          "int d, int seed, int batch_index, int n, int n_tumour) -> (Tensor, Tensor, Tensor)");
     m.def("inr_backward(Tensor weights, Tensor dlogits, Tensor scratch, int kind, int num_layers, int in_dim, int out_dim, int hidden, "
           "int fourier_freqs, int num_mods, int n) -> (Tensor, Tensor)");
     m.def("inr_sample_batch(Tensor? mods_table, Tensor seg_table, int num_mods, int h, int w, int d, int seed, int batch_index, int n) "
@@ -514,6 +590,8 @@ TORCH_LIBRARY_IMPL(mrirt_native, CompositeExplicitAutograd, m) {
     m.impl("inr_forward", &inr_forward);
     m.impl("inr_forward_f32", &inr_forward_f32);
     m.impl("inr_loss", &inr_loss);
+    m.impl("inr_loss_ext", &inr_loss_ext);
+    m.impl("inr_sample_batch_mix", &inr_sample_batch_mix);
     m.impl("inr_backward", &inr_backward);
     m.impl("inr_sample_batch", &inr_sample_batch);
     m.impl("inr_adamw_step", &inr_adamw_step);

@@ -496,10 +496,55 @@ def forward_f32(desc: _lib.InrDesc, w_flat: torch.Tensor, b_flat: torch.Tensor, 
     return logits
 
 
+def loss_ext(class_weights, dice_weight: float = 0.0, per_class_dice: bool = False, focal_gamma: float = 0.0, focal_alpha=None,
+             label_smoothing: float = 0.0, edema_fp_weight: float = 0.0, tversky_edema_alpha: float = 0.8, tversky_edema_beta: float = 0.2,
+             tversky_edema_weight: float = 0.0, edema_logit_reg: float = 0.0, edema_class: int = 2) -> _lib.InrLossExt:
+    """``MrirtInrLossExt`` from the loss flags of scripts/jax_inr_brats.py (``--dice-weight``, ``--per-class-dice``,
+    ``--focal-gamma``, ``--focal-alpha``, ``--label-smoothing``, ``--edema-fp-weight``, ``--tversky-edema-alpha / -beta /
+    -weight``, ``--edema-logit-reg``, ``--class-weights``) with the script's defaults: without ``per_class_dice`` the Dice is
+    prevalence-weighted.  ``edema_class`` is the script's 2.  The library checks the values when the struct is used."""
+    x = _lib.InrLossExt()
+    cw = [float(np.float32(v)) for v in np.asarray(class_weights, dtype=np.float32).reshape(-1)]
+    if len(cw) > 16:
+        raise ValueError("at most 16 classes")
+    for k, v in enumerate(cw):
+        x.classWeights[k] = v
+    flags = _lib.LOSS_PER_CLASS_DICE if per_class_dice else 0
+    if focal_alpha is not None:
+        fa = [float(np.float32(v)) for v in np.asarray(focal_alpha, dtype=np.float32).reshape(-1)]
+        if len(fa) != len(cw):
+            raise ValueError(f"focal_alpha holds {len(fa)} values for {len(cw)} class weights")
+        for k, v in enumerate(fa):
+            x.focalAlpha[k] = v
+        flags |= _lib.LOSS_FOCAL_ALPHA
+    x.diceWeight, x.focalGamma, x.labelSmoothing = float(dice_weight), float(focal_gamma), float(label_smoothing)
+    x.edemaFpWeight, x.tverskyAlpha, x.tverskyBeta = float(edema_fp_weight), float(tversky_edema_alpha), float(tversky_edema_beta)
+    x.tverskyWeight, x.edemaLogitReg, x.edemaClass, x.flags = float(tversky_edema_weight), float(edema_logit_reg), int(edema_class), flags
+    return x
+
+
+def _loss_ext_and_dlogits(logits: torch.Tensor, labels: torch.Tensor, ext: _lib.InrLossExt, want_grad: bool):
+    n, nc = int(logits.shape[0]), int(logits.shape[1])
+    dev = logits.device
+    scratch = torch.empty(max(int(_lib.lib().mrirt_inr_loss_ext_scratch_bytes(n)), 16), dtype=torch.uint8, device=dev)
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    aux = torch.empty((2, nc), dtype=torch.float32, device=dev)
+    terms = torch.empty(5, dtype=torch.float32, device=dev)
+    dl = torch.empty_like(logits) if want_grad else None
+    rc = _lib.lib().mrirt_inr_loss_ext(_ptr(logits), _ptr(labels), n, nc, C.byref(ext), _ptr(loss), _ptr(aux), _ptr(terms), _ptr(dl),
+                                       _ptr(scratch), scratch.numel(), _stream_ptr(None))
+    _lib.check(rc, "mrirt_inr_loss_ext")
+    return loss.reshape(()), aux, dl, terms
+
+
 def loss_and_dlogits(logits: torch.Tensor, labels: torch.Tensor, class_weights, dice_weight: float, scratch=None,
-                     want_grad: bool = True):
+                     want_grad: bool = True, ext: Optional[_lib.InrLossExt] = None):
     """``mrirt_inr_loss`` on (n, C) logits and int32 labels: (loss 0-d, aux (2, C): CE per class, Dice per class,
-    dlogits (n, C) or None), all on the device."""
+    dlogits (n, C) or None), all on the device.  With ``ext`` (``loss_ext(...)``) the loss is ``mrirt_inr_loss_ext``'s —
+    ``class_weights`` / ``dice_weight`` are then not read, the loss sums get a scratch of their own — and a fourth value is
+    returned: terms (5,) = CE, Dice loss, edema FP / n, Tversky index, logit-regulariser mean."""
+    if ext is not None:
+        return _loss_ext_and_dlogits(logits, labels, ext, want_grad)
     n, nc = int(logits.shape[0]), int(logits.shape[1])
     cw = [float(np.float32(v)) for v in class_weights]
     if len(cw) != nc:
@@ -538,12 +583,13 @@ def _split_grads(gw: torch.Tensor, gb: torch.Tensor, dims: Sequence[int]):
     return out
 
 
-def make_loss_and_grad(num_classes: int, class_weights, dice_weight: float, fourier_freqs: int):
+def make_loss_and_grad(num_classes: int, class_weights, dice_weight: float, fourier_freqs: int, ext: Optional[_lib.InrLossExt] = None):
     """inr/inr/model.py:64-90 on the GPU: returns ``f(params, coords, intensities, labels) -> ((loss, aux), grads)`` with the
     reference's return shape — ``loss`` a 0-d device tensor, ``aux = {"ce_per_class", "dice_per_class"}`` (device, (C,)),
     ``grads`` a list of ``{"W", "b"}`` device tensors shaped like ``params`` (NumPy arrays or device tensors);
     ``intensities`` may be None for a network without modalities.  One fp32
-    forward, the loss and one backward pass (csrc/inr_train.hip); nothing synchronises with the host."""
+    forward, the loss and one backward pass (csrc/inr_train.hip); nothing synchronises with the host.  ``ext``
+    (``loss_ext(...)``): the loss is ``mrirt_inr_loss_ext``'s and ``aux`` gains ``"terms"`` (5,)."""
     cw = [float(v) for v in np.asarray(class_weights, dtype=np.float32).reshape(-1)]
     if len(cw) != int(num_classes):
         raise ValueError(f"class_weights holds {len(cw)} values for {num_classes} classes")
@@ -562,9 +608,9 @@ def make_loss_and_grad(num_classes: int, class_weights, dice_weight: float, four
         w_flat, b_flat = torch.cat([W.reshape(-1) for W in Ws]), torch.cat(bs)
         scratch = train_scratch(desc, n, dev)
         logits = forward_f32(desc, w_flat, b_flat, c, f, n, scratch)
-        loss, aux, dl = loss_and_dlogits(logits, lab, cw, dice_weight, scratch)
+        loss, aux, dl, *terms = loss_and_dlogits(logits, lab, cw, dice_weight, scratch, ext=ext)
         gw, gb = backward_f32(desc, w_flat, n, dl, scratch)
-        return (loss, {"ce_per_class": aux[0], "dice_per_class": aux[1]}), _split_grads(gw, gb, dims)
+        return (loss, {"ce_per_class": aux[0], "dice_per_class": aux[1], **({"terms": terms[0]} if terms else {})}), _split_grads(gw, gb, dims)
 
     return loss_and_grad
 
@@ -632,14 +678,45 @@ class VoxelCache:
         c.ncases, c.numMods = self.n_cases, M
         c.hwd[0], c.hwd[1], c.hwd[2] = shape
         self.desc = c
+        self._tumour = None
 
-    def sample(self, seed: int, batch_index: int, n: int):
+    def tumour_index(self) -> _lib.InrTumourIndex:
+        """``MrirtInrTumourIndex`` of the cache: the flat offsets of every case's voxels with seg > 0, ascending, built on the
+        first call by ``mrirt_inr_tumour_count`` (one read of the per-case counts: load time) and ``mrirt_inr_tumour_index``,
+        and kept alive with the cache (``tumour_offsets`` int64 (ncases + 1,), ``tumour_voxels`` a uint32 array viewed as int32)."""
+        if self._tumour is None:
+            lib, dev = _lib.lib(), self.device
+            counts = torch.empty(self.n_cases, dtype=torch.int64, device=dev)
+            _lib.check(lib.mrirt_inr_tumour_count(C.byref(self.desc), _ptr(counts), _stream_ptr(None)), "mrirt_inr_tumour_count")
+            offsets = torch.zeros(self.n_cases + 1, dtype=torch.int64)
+            offsets[1:] = torch.cumsum(counts.cpu(), 0)
+            self.tumour_offsets = offsets.to(dev)
+            self.tumour_voxels = torch.empty(max(int(offsets[-1]), 1), dtype=torch.int32, device=dev)
+            nbytes = int(lib.mrirt_inr_tumour_index_scratch_bytes(C.byref(self.desc)))
+            if nbytes <= 0:
+                raise ValueError("tumour_index: the volume has 2^32 voxels or more")
+            scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            _lib.check(lib.mrirt_inr_tumour_index(C.byref(self.desc), _ptr(self.tumour_offsets), _ptr(self.tumour_voxels), _ptr(scratch), nbytes,
+                                                  _stream_ptr(None)), "mrirt_inr_tumour_index")
+            torch.cuda.current_stream(dev).synchronize()          # the scratch dies here
+            self._tumour = _lib.InrTumourIndex(self.tumour_voxels.data_ptr(), self.tumour_offsets.data_ptr())
+        return self._tumour
+
+    def sample(self, seed: int, batch_index: int, n: int, n_tumour: int = 0):
         """Micro-batch ``batch_index`` of the stream ``seed`` (``mrirt_inr_sample_batch``): (coords (n, 3) fp32,
-        intensities (n, M) fp32, labels (n,) int32) on the device — the return order of the reference's ``sample_batch``."""
+        intensities (n, M) fp32, labels (n,) int32) on the device — the return order of the reference's ``sample_batch``.
+        ``n_tumour > 0``: the first ``n_tumour`` points are drawn from the tumour voxels (``mrirt_inr_sample_batch_mix``; the
+        other points keep their bits)."""
         dev = self.device
         coords = torch.empty((int(n), 3), dtype=torch.float32, device=dev)
         feats = torch.empty((int(n), self.n_modalities), dtype=torch.float32, device=dev)
         labels = torch.empty(int(n), dtype=torch.int32, device=dev)
+        if int(n_tumour) != 0:
+            rc = _lib.lib().mrirt_inr_sample_batch_mix(C.byref(self.desc), C.byref(self.tumour_index()), int(seed) & (2 ** 64 - 1),
+                                                       int(batch_index) & (2 ** 64 - 1), int(n), int(n_tumour), _ptr(coords),
+                                                       _ptr(feats) if self.n_modalities else None, _ptr(labels), _stream_ptr(None))
+            _lib.check(rc, "mrirt_inr_sample_batch_mix")
+            return coords, feats, labels
         rc = _lib.lib().mrirt_inr_sample_batch(C.byref(self.desc), int(seed) & (2 ** 64 - 1), int(batch_index) & (2 ** 64 - 1), int(n),
                                                _ptr(coords), _ptr(feats) if self.n_modalities else None, _ptr(labels), _stream_ptr(None))
         _lib.check(rc, "mrirt_inr_sample_batch")
@@ -749,9 +826,12 @@ def train_cfg(micro_batch: int, accum: int, seed: int, class_weights, dice_weigh
     return c
 
 
-def _run_entry(desc: _lib.InrDesc, muon: Optional[_lib.Muon]):
+def _run_entry(desc: _lib.InrDesc, muon: Optional[_lib.Muon], ext: Optional[_lib.InrTrainExt] = None):
     """(name, scratch-size function, run function taking (desc, cache, cfg, state, ...)) of the one-call run for ``desc``."""
     lib = _lib.lib()
+    if ext is not None:
+        size, run = lib.mrirt_inr_train_run_ext_scratch_bytes, lib.mrirt_inr_train_run_ext
+        return "mrirt_inr_train_run_ext", lambda d, c, g: size(d, c, g, C.byref(ext)), lambda d, c, g, *rest: run(d, c, g, C.byref(ext), *rest)
     if muon is not None:
         run = lib.mrirt_inr_train_run_muon
         return "mrirt_inr_train_run_muon", lib.mrirt_inr_train_run_muon_scratch_bytes, lambda d, c, g, *rest: run(d, c, g, C.byref(muon), *rest)
@@ -759,19 +839,45 @@ def _run_entry(desc: _lib.InrDesc, muon: Optional[_lib.Muon]):
     return f"mrirt_{family}_train_run", getattr(lib, f"mrirt_{family}_train_run_scratch_bytes"), getattr(lib, f"mrirt_{family}_train_run")
 
 
+def n_tumour_of(micro_batch: int, tumor_ratio: float) -> int:
+    """jax_inr_brats.py:467-468: ``int(micro_batch * clip(tumor_ratio, 0, 1))`` in double."""
+    return int(float(int(micro_batch)) * min(max(float(tumor_ratio), 0.0), 1.0))
+
+
+def train_ext(cache: Optional[VoxelCache] = None, loss: Optional[_lib.InrLossExt] = None, muon: Optional[_lib.Muon] = None,
+              n_tumour: int = 0) -> _lib.InrTrainExt:
+    """``MrirtInrTrainExt`` for ``train_run(..., ext=)``: any of the extended loss (``loss_ext(...)``), Muon (``muon_hp(...)``)
+    and ``n_tumour`` tumour draws per micro-batch (needs ``cache``, whose tumour index is built here).  The struct keeps the
+    objects it points to alive."""
+    x = _lib.InrTrainExt()
+    if loss is not None:
+        x.loss = C.pointer(loss)
+    if muon is not None:
+        x.muon = C.pointer(muon)
+    if int(n_tumour) != 0:
+        if cache is None:
+            raise ValueError("train_ext: n_tumour needs the cache whose tumour index to use")
+        x.tumour = cache.tumour_index()
+    x.nTumour = int(n_tumour)
+    x._keep = (loss, muon, cache)
+    return x
+
+
 def train_run(desc: _lib.InrDesc, cache: VoxelCache, cfg: _lib.InrTrainCfg, st: AdamWState, steps: int, scratch: Optional[torch.Tensor] = None,
-              muon: Optional[_lib.Muon] = None):
+              muon: Optional[_lib.Muon] = None, ext: Optional[_lib.InrTrainExt] = None):
     """``mrirt_inr_train_run`` (``mrirt_siren_train_run`` for a SIREN descriptor): ``steps`` optimiser steps from ``st.step``
     on, enqueued in one call without a host
     synchronisation.  Returns the device tensor history (steps, accum, 1 + 2 C): loss, CE per class, Dice per class of every
     micro-batch.  ``st`` is updated in place and ``st.step`` advanced.  ``muon`` (``muon_hp(...)``): the update is Muon on the
     weight matrices and AdamW on the biases (``mrirt_inr_train_run_muon``); ``cfg.adamw`` then is the bias / clip half and
-    ``st.nu_w`` is left alone."""
-    where, run_bytes, run = _run_entry(desc, muon)
+    ``st.nu_w`` is left alone.  ``ext`` (``train_ext(...)``): the run is ``mrirt_inr_train_run_ext`` with its loss, optimiser
+    and sampler (``muon`` is then not read: the optimiser is ``ext``'s)."""
+    where, run_bytes, run = _run_entry(desc, muon, ext)
     nbytes = int(run_bytes(C.byref(desc), C.byref(cache.desc), C.byref(cfg)))
     if nbytes <= 0:
         raise ValueError("train_run: unsupported network / cache / configuration (Fourier ReLU or SIREN kind over the cache's modalities, "
-                         "accum >= 1, decay_steps > warmup_steps, finite hyper-parameters)")
+                         "accum >= 1, decay_steps > warmup_steps, finite hyper-parameters; with ext: loss options in their domains, "
+                         "0 <= n_tumour <= micro-batch)")
     if scratch is None or scratch.numel() < nbytes:
         scratch = torch.empty(nbytes, dtype=torch.uint8, device=st.w.device)
     hist = torch.empty((int(steps), int(cfg.accum), 1 + 2 * int(desc.outDim)), dtype=torch.float32, device=st.w.device)
@@ -848,6 +954,29 @@ def _optimizer_of(config: Dict[str, Any]) -> Optional[_lib.Muon]:
                    ns_steps=int(config.get("MUON_NS_STEPS", MUON_NS_STEPS)), weight_decay=float(config.get("MUON_WEIGHT_DECAY", MUON_WEIGHT_DECAY)))
 
 
+# the optional config keys of the extended loss and the sampling mix (the flags of scripts/jax_inr_brats.py), with the value
+# each takes when another of them is present
+EXT_CONFIG_KEYS = dict(FOCAL_GAMMA=0.0, FOCAL_ALPHA=None, LABEL_SMOOTHING=0.0, PER_CLASS_DICE=True, EDEMA_FP_WEIGHT=0.0, TVERSKY_EDEMA_ALPHA=0.8,
+                       TVERSKY_EDEMA_BETA=0.2, TVERSKY_EDEMA_WEIGHT=0.0, EDEMA_LOGIT_REG=0.0, EDEMA_CLASS=2, TUMOR_RATIO=0.0)
+
+
+def _ext_keys_of(config: Dict[str, Any]) -> Dict[str, Any]:
+    """The keys of EXT_CONFIG_KEYS the config holds (None values dropped): empty = today's run, untouched."""
+    return {k: config[k] for k in EXT_CONFIG_KEYS if k in config and config[k] is not None}
+
+
+def loss_ext_of_config(config: Dict[str, Any], nc: int) -> _lib.InrLossExt:
+    """The ``MrirtInrLossExt`` a ``train_inr`` / ``train_siren`` config stands for: CLASS_WEIGHTS, DICE_WEIGHT and the optional keys
+    of EXT_CONFIG_KEYS at their defaults where absent (PER_CLASS_DICE True: the Dice of model.py)."""
+    g = {k: config.get(k, v) for k, v in EXT_CONFIG_KEYS.items()}
+    cw = list(config["CLASS_WEIGHTS"])
+    if len(cw) != nc:
+        raise ValueError(f"CLASS_WEIGHTS holds {len(cw)} values for {nc} classes")
+    return loss_ext(cw, float(config["DICE_WEIGHT"]), bool(g["PER_CLASS_DICE"]), float(g["FOCAL_GAMMA"]), g["FOCAL_ALPHA"], float(g["LABEL_SMOOTHING"]),
+                    float(g["EDEMA_FP_WEIGHT"]), float(g["TVERSKY_EDEMA_ALPHA"]), float(g["TVERSKY_EDEMA_BETA"]), float(g["TVERSKY_EDEMA_WEIGHT"]),
+                    float(g["EDEMA_LOGIT_REG"]), int(g["EDEMA_CLASS"]))
+
+
 def _load_resume(path) -> Tuple[List[Dict[str, np.ndarray]], Optional[Dict[str, np.ndarray]]]:
     """A checkpoint's parameters — the periodic W_i / b_i layout read directly (no pickle), anything else through
     ``model_load`` — and, when the optimiser file this loop writes beside it exists, the moments and the step count."""
@@ -887,6 +1016,7 @@ def _train_loop(config: Dict[str, Any], cases_or_cache, val_cases, params, resum
     lr_schedule(float(config["LR"]), float(config["MIN_LR"]), warmup, decay_steps, 0)          # refuses T <= 0 before any work
     muon = _optimizer_of(config)
     name = "muon" if muon is not None else "adamw"
+    ext_keys = _ext_keys_of(config)
     opt = None
     if resume_from is not None:                          # read, and refused if it is the other optimiser's, before any GPU work
         params, opt = _load_resume(resume_from)
@@ -917,12 +1047,15 @@ def _train_loop(config: Dict[str, Any], cases_or_cache, val_cases, params, resum
     loss_history: List[float] = []
     dice_history: List[List[float]] = [[] for _ in range(nc)]
     ce_history: List[List[float]] = [[] for _ in range(nc)]
-    nbytes = int(_run_entry(desc, muon)[1](C.byref(desc), C.byref(cache.desc), C.byref(cfg)))
+    ext = None
+    if ext_keys:                                         # any key of EXT_CONFIG_KEYS: the run is mrirt_inr_train_run_ext
+        ext = train_ext(cache, loss_ext_of_config(config, nc), muon, n_tumour_of(micro, config.get("TUMOR_RATIO", 0.0)))
+    nbytes = int(_run_entry(desc, muon, ext)[1](C.byref(desc), C.byref(cache.desc), C.byref(cfg)))
     scratch = torch.empty(nbytes, dtype=torch.uint8, device=cache.device) if nbytes > 0 else None      # one buffer for every chunk
     while st.step < train_steps:
         first = st.step
         steps = min(train_steps, (first // every + 1) * every, first + 4096) - first
-        h = train_run(desc, cache, cfg, st, steps, scratch, muon).cpu().numpy().astype(np.float64).mean(axis=1)     # per-step means
+        h = train_run(desc, cache, cfg, st, steps, scratch, muon, ext).cpu().numpy().astype(np.float64).mean(axis=1)     # per-step means
         for k in range(steps):
             loss_history.append(float(h[k, 0]))
             for c in range(nc):
@@ -941,6 +1074,7 @@ def _train_loop(config: Dict[str, Any], cases_or_cache, val_cases, params, resum
             ck = save_path / CHECKPOINT_BASENAME.format(step=st.step)
             np.savez_compressed(ck, **flat)
             np.savez_compressed(ck.with_name(ck.stem + "_opt.npz"), step=np.int64(st.step), **({"optimizer": np.str_("muon")} if muon is not None else {}),
+                                **{"ext_" + k: np.asarray(v, np.float64) for k, v in ext_keys.items()},
                                 **{k: getattr(st, k).cpu().numpy() for k in ("mu_w", "mu_b", "nu_w", "nu_b")})
     state = {"train_cache": cache, "val_cache": val_cache, "vol_shape": cache.vol_shape, "loss_history": loss_history,
              "dice_history": dice_history, "ce_history": ce_history, "best_val_dice": None, "best_step": None, "save_path": save_path,
@@ -965,6 +1099,11 @@ def train_inr(config: Dict[str, Any], cases_or_cache, val_cases=None, params=Non
     AdamW on the biases, inside ``mrirt_inr_train_run_muon`` (optional MUON_BETA, MUON_NS_STEPS, MUON_NESTEROV,
     MUON_WEIGHT_DECAY; optax's defaults otherwise); any other value keeps AdamW.  A Muon run's ``_opt.npz`` carries
     ``optimizer = "muon"``; resuming a state with the other optimiser raises ``ValueError``.
+    The optional keys FOCAL_GAMMA, FOCAL_ALPHA, LABEL_SMOOTHING, PER_CLASS_DICE (default True: the Dice of model.py),
+    EDEMA_FP_WEIGHT, TVERSKY_EDEMA_ALPHA / _BETA / _WEIGHT, EDEMA_LOGIT_REG, EDEMA_CLASS (default 2) and TUMOR_RATIO (default 0)
+    are the loss and sampling options of scripts/jax_inr_brats.py: with any of them present the run is
+    ``mrirt_inr_train_run_ext`` (``mrirt_inr_loss_ext``, and ``int(MICRO_BATCH_SIZE * clip(TUMOR_RATIO, 0, 1))`` tumour draws at
+    the head of every micro-batch); the keys in force are recorded as ``ext_<KEY>`` in ``_opt.npz``.  Without them nothing changes.
     Returns ``(params, state)``: the reference's list of ``{"W", "b"}`` (NumPy) and a dict with ``loss_history``,
     ``dice_history`` / ``ce_history`` (per class), the caches, ``vol_shape`` and ``opt`` (the ``AdamWState``)."""
     K = int(config["FOURIER_FREQS"])
@@ -1040,9 +1179,10 @@ def _siren_dict(layers) -> Dict[str, Dict[str, Any]]:
     return {f"l{i}": {"w": p["W"], "b": p["b"]} for i, p in enumerate(layers)}
 
 
-def make_siren_loss_and_grad(num_classes: int, class_weights, dice_weight: float, w0: float = 30.0):
+def make_siren_loss_and_grad(num_classes: int, class_weights, dice_weight: float, w0: float = 30.0, ext: Optional[_lib.InrLossExt] = None):
     """``make_loss_and_grad`` for the notebook's SIREN: ``f(params, coords, intensities, labels) -> ((loss, aux), grads)`` with
-    ``params`` the dict ``l{i} -> {"w", "b"}`` and ``grads`` a dict of device tensors shaped like it.  x = (coords, intensities)."""
+    ``params`` the dict ``l{i} -> {"w", "b"}`` and ``grads`` a dict of device tensors shaped like it.  x = (coords, intensities).
+    ``ext`` as in ``make_loss_and_grad``."""
     cw = [float(v) for v in np.asarray(class_weights, dtype=np.float32).reshape(-1)]
     if len(cw) != int(num_classes):
         raise ValueError(f"class_weights holds {len(cw)} values for {num_classes} classes")
@@ -1061,9 +1201,9 @@ def make_siren_loss_and_grad(num_classes: int, class_weights, dice_weight: float
         w_flat, b_flat = torch.cat([W.reshape(-1) for W in Ws]), torch.cat(bs)
         scratch = siren_train_scratch(desc, n, dev)
         logits = siren_forward_f32(desc, w_flat, b_flat, c, f, n, scratch)
-        loss, aux, dl = loss_and_dlogits(logits, lab, cw, dice_weight, scratch)
+        loss, aux, dl, *terms = loss_and_dlogits(logits, lab, cw, dice_weight, scratch, ext=ext)
         gw, gb = siren_backward_f32(desc, w_flat, n, dl, scratch)
-        return (loss, {"ce_per_class": aux[0], "dice_per_class": aux[1]}), _siren_dict(_split_grads(gw, gb, dims))
+        return (loss, {"ce_per_class": aux[0], "dice_per_class": aux[1], **({"terms": terms[0]} if terms else {})}), _siren_dict(_split_grads(gw, gb, dims))
 
     return loss_and_grad
 

@@ -539,6 +539,52 @@ def _(logits, labels, class_weights, dice_weight):
             torch.empty((2, logits.shape[1]), dtype=torch.float32, device=logits.device), torch.empty_like(logits))
 
 
+@torch.library.custom_op("mrirt::inr_loss_ext", mutates_args=())
+def inr_loss_ext(logits: torch.Tensor, labels: torch.Tensor, class_weights: Sequence[float], focal_alpha: Sequence[float], dice_weight: float,
+                 per_class_dice: bool, focal_gamma: float, label_smoothing: float, edema_fp_weight: float, tversky_alpha: float,
+                 tversky_beta: float, tversky_weight: float, edema_logit_reg: float,
+                 edema_class: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(loss fp32 [1], aux fp32 [2, C], terms fp32 [5]: CE, Dice loss, edema FP / n, Tversky index, logit-regulariser mean,
+    dlogits fp32 [n, C]) of mrirt_inr_loss_ext (scripts/jax_inr_brats.py:205-257) on logits [n, C] and int32 labels [n].
+    An empty ``focal_alpha`` leaves the focal factor unweighted."""
+    z = _dev_flat(logits, torch.float32, "logits")
+    lab = _dev_flat(labels, torch.int32, "labels")
+    if z.dim() != 2 or z.shape[0] < 1 or lab.numel() != z.shape[0]:
+        raise ValueError("logits must be [n, C] with n >= 1 and labels [n]")
+    n, nc = int(z.shape[0]), int(z.shape[1])
+    if not 1 <= nc <= 16 or len(class_weights) != nc or len(focal_alpha) not in (0, nc):
+        raise ValueError("1..16 classes, one class weight each, focal_alpha empty or one value per class")
+    x = _lib.InrLossExt()
+    for k in range(nc):
+        x.classWeights[k] = float(class_weights[k])
+        if len(focal_alpha):
+            x.focalAlpha[k] = float(focal_alpha[k])
+    x.diceWeight, x.focalGamma, x.labelSmoothing = float(dice_weight), float(focal_gamma), float(label_smoothing)
+    x.edemaFpWeight, x.tverskyAlpha, x.tverskyBeta = float(edema_fp_weight), float(tversky_alpha), float(tversky_beta)
+    x.tverskyWeight, x.edemaLogitReg, x.edemaClass = float(tversky_weight), float(edema_logit_reg), int(edema_class)
+    x.flags = (_lib.LOSS_PER_CLASS_DICE if per_class_dice else 0) | (_lib.LOSS_FOCAL_ALPHA if len(focal_alpha) else 0)
+    dev = _one_device([("logits", z), ("labels", lab)])
+    lib = _lib.lib()
+    with torch.cuda.device(dev):
+        nbytes = int(lib.mrirt_inr_loss_ext_scratch_bytes(n))
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        aux = torch.empty((2, nc), dtype=torch.float32, device=dev)
+        terms = torch.empty(5, dtype=torch.float32, device=dev)
+        dl = torch.empty_like(z)
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        rc = lib.mrirt_inr_loss_ext(_ptr(z), _ptr(lab), n, nc, C.byref(x), _ptr(loss), _ptr(aux), _ptr(terms), _ptr(dl), _ptr(scratch), nbytes,
+                                    _stream())
+    _lib.check(rc, "mrirt_inr_loss_ext")
+    return loss, aux, terms, dl
+
+
+@inr_loss_ext.register_fake
+def _(logits, labels, class_weights, focal_alpha, dice_weight, per_class_dice, focal_gamma, label_smoothing, edema_fp_weight, tversky_alpha,
+      tversky_beta, tversky_weight, edema_logit_reg, edema_class):
+    return (torch.empty(1, dtype=torch.float32, device=logits.device), torch.empty((2, logits.shape[1]), dtype=torch.float32, device=logits.device),
+            torch.empty(5, dtype=torch.float32, device=logits.device), torch.empty_like(logits))
+
+
 @torch.library.custom_op("mrirt::inr_backward", mutates_args=())
 def inr_backward(weights: torch.Tensor, dlogits: torch.Tensor, scratch: torch.Tensor, kind: int, num_layers: int, in_dim: int,
                  out_dim: int, hidden: int, fourier_freqs: int, num_mods: int, n: int) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -598,6 +644,43 @@ def inr_sample_batch(mods_table: Optional[torch.Tensor], seg_table: torch.Tensor
 
 @inr_sample_batch.register_fake
 def _(mods_table, seg_table, num_mods, h, w, d, seed, batch_index, n):
+    dev = seg_table.device
+    return (torch.empty((n, 3), dtype=torch.float32, device=dev), torch.empty((n, num_mods), dtype=torch.float32, device=dev),
+            torch.empty(n, dtype=torch.int32, device=dev))
+
+
+@torch.library.custom_op("mrirt::inr_sample_batch_mix", mutates_args=())
+def inr_sample_batch_mix(mods_table: Optional[torch.Tensor], seg_table: torch.Tensor, tumour_index: Optional[torch.Tensor],
+                         tumour_offsets: Optional[torch.Tensor], num_mods: int, h: int, w: int, d: int, seed: int, batch_index: int, n: int,
+                         n_tumour: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``inr_sample_batch`` with the first ``n_tumour`` points drawn from the tumour voxels (mrirt_inr_sample_batch_mix):
+    ``tumour_index`` holds the uint32 voxel offsets in an int32 device tensor, ``tumour_offsets`` is int64 [ncases + 1]
+    (``VoxelCache.tumour_voxels`` / ``tumour_offsets``); both may be None when ``n_tumour`` is 0."""
+    st = _dev_flat(seg_table, torch.int64, "seg_table")
+    mt = _dev_flat(mods_table, torch.int64, "mods_table")
+    ti = _dev_flat(tumour_index, torch.int32, "tumour_index")
+    to = _dev_flat(tumour_offsets, torch.int64, "tumour_offsets")
+    if st.numel() < 1 or (num_mods > 0 and (mt is None or mt.numel() != st.numel())):
+        raise ValueError("seg_table must hold one address per case, and mods_table as many when num_mods > 0")
+    if n_tumour != 0 and (ti is None or to is None or to.numel() != st.numel() + 1):
+        raise ValueError("n_tumour > 0 needs tumour_index and tumour_offsets [ncases + 1]")
+    dev = _one_device([("seg_table", st), ("mods_table", mt), ("tumour_index", ti), ("tumour_offsets", to)])
+    c = _lib.InrCache()
+    c.mods, c.seg, c.ncases, c.numMods = (mt.data_ptr() if num_mods > 0 else None), st.data_ptr(), st.numel(), num_mods
+    c.hwd[0], c.hwd[1], c.hwd[2] = h, w, d
+    t = _lib.InrTumourIndex(ti.data_ptr(), to.data_ptr()) if n_tumour != 0 else None
+    with torch.cuda.device(dev):
+        coords = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        feats = torch.empty((n, num_mods), dtype=torch.float32, device=dev)
+        labels = torch.empty(n, dtype=torch.int32, device=dev)
+        rc = _lib.lib().mrirt_inr_sample_batch_mix(C.byref(c), C.byref(t) if t is not None else None, _u64(seed), _u64(batch_index), int(n),
+                                                   int(n_tumour), _ptr(coords), _ptr(feats) if num_mods > 0 else None, _ptr(labels), _stream())
+    _lib.check(rc, "mrirt_inr_sample_batch_mix")
+    return coords, feats, labels
+
+
+@inr_sample_batch_mix.register_fake
+def _(mods_table, seg_table, tumour_index, tumour_offsets, num_mods, h, w, d, seed, batch_index, n, n_tumour):
     dev = seg_table.device
     return (torch.empty((n, 3), dtype=torch.float32, device=dev), torch.empty((n, num_mods), dtype=torch.float32, device=dev),
             torch.empty(n, dtype=torch.int32, device=dev))

@@ -12,8 +12,14 @@ clipping.  Loss and per-class Dice of the whole volume are printed before and af
 the exact-sine step of DESIGN.md section 16); the fitted dict goes through ``pack_mlp(params, KIND_SIREN, 0, 4, w0)`` and
 ``classify``, and the Dice of those classes against the labels is the last line.
 
+The loss and sampling flags of the reference's scripts/jax_inr_brats.py are taken under their own names (--focal-gamma,
+--focal-alpha a,b,c,d, --label-smoothing, --per-class-dice / --no-per-class-dice, --edema-fp-weight, --tversky-edema-alpha / -beta /
+-weight, --edema-logit-reg, --tumor-ratio): with any of them the fit runs through ``mrirt_inr_train_run_ext`` (DESIGN.md section
+18) and the whole-volume loss printed is the extended one; without them nothing changes.
+
     python tools/inr_fit.py [--size 48] [--steps 300] [--batch 4096] [--hidden 64] [--layers 4] [--freqs 4] [--lr 3e-3]
     python tools/inr_fit.py --siren [--w0 30] [--lr 1e-3] ...
+    python tools/inr_fit.py --focal-gamma 2 --tumor-ratio 0.4 --tversky-edema-weight 0.2 --no-per-class-dice
 """
 import argparse
 import pathlib
@@ -38,6 +44,16 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--siren", action="store_true", help="fit a SIREN (sine activations) instead of the Fourier/ReLU network")
     ap.add_argument("--w0", type=float, default=30.0)
+    ap.add_argument("--per-class-dice", action=argparse.BooleanOptionalAction, default=None, help="mean over classes (the default here) or prevalence-weighted Dice")
+    ap.add_argument("--focal-gamma", type=float, default=None)
+    ap.add_argument("--focal-alpha", type=str, default=None, help="comma-separated per-class alpha")
+    ap.add_argument("--label-smoothing", type=float, default=None)
+    ap.add_argument("--edema-fp-weight", type=float, default=None)
+    ap.add_argument("--tversky-edema-alpha", type=float, default=None)
+    ap.add_argument("--tversky-edema-beta", type=float, default=None)
+    ap.add_argument("--tversky-edema-weight", type=float, default=None)
+    ap.add_argument("--edema-logit-reg", type=float, default=None)
+    ap.add_argument("--tumor-ratio", type=float, default=None)
     args = ap.parse_args()
     import torch
     from mrirt import inr, synth
@@ -54,13 +70,19 @@ def main():
     counts = np.bincount(seg.reshape(-1), minlength=nc).astype(np.float64)
     cw = (counts.sum() / (nc * np.maximum(counts, 1.0))).astype(np.float32)          # inverse-frequency class weights
 
+    # the extended-loss / sampling keys the user gave, under train_inr's names; none: today's run
+    extra = {k.upper(): v for k, v in vars(args).items() if k.upper() in inr.EXT_CONFIG_KEYS and v is not None}
+    if "FOCAL_ALPHA" in extra:
+        extra["FOCAL_ALPHA"] = [float(v) for v in extra["FOCAL_ALPHA"].split(",")]
+    args.extra = extra
+    args.ext = inr.loss_ext_of_config(dict(extra, CLASS_WEIGHTS=[float(v) for v in cw], DICE_WEIGHT=args.dice_weight), nc) if extra else None
     if args.siren:
         return fit_siren(args, inr, dev, mods, seg, coords, feats, labels, cw, nc)
     params = [{k: torch.from_numpy(v).to(dev) for k, v in p.items()} for p in inr.init_mlp(args.seed, 3 + 6 * K + 4, [args.hidden] * args.layers, nc)]
-    step = inr.make_loss_and_grad(nc, cw, args.dice_weight, K)
+    step = inr.make_loss_and_grad(nc, cw, args.dice_weight, K, ext=args.ext)
     config = dict(GLOBAL_BATCH_SIZE=args.batch, MICRO_BATCH_SIZE=args.batch, FOURIER_FREQS=K, HIDDEN_DIMS=[args.hidden] * args.layers, LR=args.lr,
                   MIN_LR=args.lr, WARMUP_STEPS=0, TRAIN_STEPS=args.steps, RNG_SEED=args.seed, NUM_CLASSES=nc, DICE_WEIGHT=args.dice_weight,
-                  CLASS_WEIGHTS=[float(v) for v in cw], CLIP_NORM=float("inf"), CHECKPOINT_EVERY_STEPS=100)
+                  CLASS_WEIGHTS=[float(v) for v in cw], CLIP_NORM=float("inf"), CHECKPOINT_EVERY_STEPS=100, **args.extra)
 
     def whole_volume(tag):
         (loss, aux), _ = step(params, coords, feats, labels)
@@ -83,10 +105,10 @@ def main():
 def fit_siren(args, inr, dev, mods, seg, coords, feats, labels, cw, nc):
     import torch
     params = inr.siren_init(args.seed, 7, [args.hidden] * args.layers, nc, args.w0)
-    step = inr.make_siren_loss_and_grad(nc, cw, args.dice_weight, args.w0)
+    step = inr.make_siren_loss_and_grad(nc, cw, args.dice_weight, args.w0, ext=args.ext)
     config = dict(GLOBAL_BATCH_SIZE=args.batch, MICRO_BATCH_SIZE=args.batch, HIDDEN_DIMS=[args.hidden] * args.layers, LR=args.lr, MIN_LR=args.lr,
                   WARMUP_STEPS=0, TRAIN_STEPS=args.steps, RNG_SEED=args.seed, NUM_CLASSES=nc, DICE_WEIGHT=args.dice_weight,
-                  CLASS_WEIGHTS=[float(v) for v in cw], CLIP_NORM=float("inf"), CHECKPOINT_EVERY_STEPS=100, W0=args.w0)
+                  CLASS_WEIGHTS=[float(v) for v in cw], CLIP_NORM=float("inf"), CHECKPOINT_EVERY_STEPS=100, W0=args.w0, **args.extra)
 
     def whole_volume(tag, p):
         (loss, aux), _ = step(p, coords, feats, labels)
