@@ -1,8 +1,10 @@
 // The LDS-tiled fp32 GEMM of DESIGN.md section 14 (v_mfma_f32_16x16x4_f32), device side: staging of the two operand views and
-// the k loop that accumulates one 64 x BN block tile, as csrc/inr_train.hip's tr_gemm_kernel runs them, for kernels outside
-// that file (csrc/inr_muon.hip).  tr_gemm_kernel keeps its own copy: moving it onto this header changed its register
-// allocation, and the training step's kernels are not to change without a measurement.  The index
-// arithmetic both call lives in inr_train.h.  Device code only.
+// the k loop that accumulates one 64 x BN block tile.  gm_fetch / gm_stage serve csrc/inr_train.hip's tr_gemm_kernel and
+// csrc/inr_muon.hip's muon_gemm_kernel alike; gm_accumulate serves Muon only, and tr_gemm_kernel keeps a copy of that loop.
+// Calling gm_accumulate from tr_gemm_kernel was measured and dropped (profiles/r15_inr_shared): same
+// bits, no spills, but the forward instantiations <64,1,0,*> went from 72 to 76 registers (7 -> 6 waves per SIMD) and the
+// step at n = 65536 over 256-wide layers became 0.6 - 1.3 % slower, several times the parent's run-to-run spread.  The
+// index arithmetic lives in inr_train.h.  Device code only.
 #pragma once
 #include "inr_train.h"
 

@@ -8,8 +8,9 @@
 //   sample_mix_kernel      mrirt_inr_sample_batch with the first nTumour points drawn from the tumour index
 // The focal CE is the PRODUCT OF TWO MEANS, [(1/n) sum m ce] [(1/n) sum w]: the reference's focal_ce_loss returns a scalar,
 // which lines 230-233 then multiply by the class-weight vector and average.  It is reproduced, not repaired.
-// No float atomics, no label indexes memory, every sum over the batch is fp64 in a fixed order.  lossx_softmax is a copy of
-// inr_train.hip's point_softmax (as tr_gemm_kernel was copied for Muon): the existing kernels are not touched.
+// No float atomics, no label indexes memory, every sum over the batch is fp64 in a fixed order.  The softmax, the wave sum
+// and the sampler's write-out are inr_device.h's, shared with csrc/inr_train.hip and csrc/inr_optim.hip.
+#include "inr_device.h"
 #include "inr_lossx.h"
 #include "mrirt_host.h"
 
@@ -33,33 +34,6 @@ struct LossXArgs {
     float* terms;
     float* dlogits;
 };
-
-__device__ __forceinline__ double lx_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-
-// softmax of one point: p[k] (fp32), d[k] = z[k] - max, and log(sum exp d); log p[k] = d[k] - the returned value
-__device__ __forceinline__ float lossx_softmax(const float* z, uint32_t C, float (&p)[kLossMaxClasses], float (&d)[kLossMaxClasses]) {
-    float m = z[0];
-    for (uint32_t k = 1; k < C; ++k) m = fmaxf(m, z[k]);
-    float s = 0.0f;
-#pragma unroll
-    for (uint32_t k = 0; k < kLossMaxClasses; ++k) {
-        p[k] = 0.0f;
-        d[k] = 0.0f;
-        if (k < C) {
-            d[k] = z[k] - m;
-            p[k] = expf(d[k]);
-            s += p[k];
-        }
-    }
-    const float inv = 1.0f / s;
-#pragma unroll
-    for (uint32_t k = 0; k < kLossMaxClasses; ++k) p[k] *= inv;
-    return logf(s);
-}
 
 // What both passes need of one point.  y[k] = yh (1 - eps) + eps / C (exactly yh for eps == 0); ce = sum_k y_k (ls - d_k):
 // for eps == 0 the one non-zero term, logf(s) - d_label, as mrirt_inr_loss forms it.
@@ -104,7 +78,7 @@ __global__ __launch_bounds__(kLossThreads) void lossx_partial_kernel(LossXArgs a
         float p[kLossMaxClasses], d[kLossMaxClasses], y[kLossMaxClasses];
         const int32_t label = a.labels[i];
         const float* z = a.logits + i * a.C;
-        const float ls = lossx_softmax(z, a.C, p, d);
+        const float ls = logf(point_softmax(z, a.C, p, d));
         const LxPoint r = lossx_point(a, label, ls, p, d, y);
         float q = 0.0f, ze = 0.0f;
 #pragma unroll
@@ -133,7 +107,7 @@ __global__ __launch_bounds__(kLossThreads) void lossx_partial_kernel(LossXArgs a
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
 #pragma unroll
     for (uint32_t v = 0; v < kLossXVals; ++v) {
-        const double s = lx_wave_sum(acc[v]);
+        const double s = wave_sum(acc[v]);
         if (lane == 0) part[wave][v] = s;
     }
     __syncthreads();
@@ -240,7 +214,7 @@ __global__ __launch_bounds__(kLossThreads) void lossx_grad_kernel(LossXArgs a) {
     float p[kLossMaxClasses], d[kLossMaxClasses], y[kLossMaxClasses];
     const int32_t label = a.labels[i];
     const float* z = a.logits + i * a.C;
-    const float ls = lossx_softmax(z, a.C, p, d);
+    const float ls = logf(point_softmax(z, a.C, p, d));
     const LxPoint r = lossx_point(a, label, ls, p, d, y);
     const float ceScale = (a.dw > 0.0f ? 1.0f - a.dw : 1.0f) * (a.focal ? sh[0] : r.w) / (float)a.n;
     float m = 1.0f, fg = 0.0f;                           // the focal factor and its p-path coefficient
@@ -401,21 +375,7 @@ __global__ __launch_bounds__(kOptThreads) void sample_mix_kernel(MixArgs a) {
             if ((int64_t)v < a.hwd) tum_decode(v, a.W, a.D, p.x, p.y, p.z);      // a foreign index cannot point outside the volume
         }
     }
-    const int64_t v = voxel_offset(p.x, p.y, p.z, a.W, a.D);
-    a.coords[3 * i + 0] = sample_coord(p.x, a.H);
-    a.coords[3 * i + 1] = sample_coord(p.y, a.W);
-    a.coords[3 * i + 2] = sample_coord(p.z, a.D);
-    a.labels[i] = (int32_t)a.seg[p.cs][v];
-    if (a.M) {
-        const float* m = a.mods[p.cs];
-        for (uint32_t k = 0; k < a.M; ++k) a.feats[i * a.M + k] = m[mod_offset(k, v, a.hwd)];
-    }
-}
-
-static int lx_check_scratch(const void* scratch, int64_t have, uint64_t need) {
-    if (!scratch) return MRIRT_ERR_NULL;
-    if (((uintptr_t)scratch & 15u) != 0 || have < 0 || (uint64_t)have < need) return MRIRT_ERR_ARG;
-    return MRIRT_OK;
+    sample_write(i, p, a.mods, a.seg, a.M, a.H, a.W, a.D, a.hwd, a.coords, a.feats, a.labels);
 }
 
 static int tum_check_cache(const MrirtInrCache* c) {
@@ -448,7 +408,7 @@ extern "C" int mrirt_inr_loss_ext(const float* logits, const int32_t* labels, in
     if (n < 1 || n >= (1ll << 31)) return MRIRT_ERR_ARG;
     int rc = lossx_check(ext, num_classes);
     if (rc != MRIRT_OK) return rc;
-    if ((rc = lx_check_scratch(scratch, scratch_bytes, lossx_scratch_bytes(n))) != MRIRT_OK) return rc;
+    if ((rc = check_scratch(scratch, scratch_bytes, lossx_scratch_bytes(n))) != MRIRT_OK) return rc;
     LossXArgs a = {};
     a.logits = logits; a.labels = labels; a.n = n; a.C = num_classes;
     for (uint32_t k = 0; k < kLossMaxClasses; ++k) a.alpha[k] = 1.0f;
@@ -498,7 +458,7 @@ extern "C" int mrirt_inr_tumour_index(const MrirtInrCache* cache, const int64_t*
     int rc = tum_check_cache(cache);
     if (rc != MRIRT_OK) return rc;
     TumArgs a = tum_args(cache);
-    if ((rc = lx_check_scratch(scratch, scratch_bytes, tum_scratch_bytes(a.ncases, a.hwd))) != MRIRT_OK) return rc;
+    if ((rc = check_scratch(scratch, scratch_bytes, tum_scratch_bytes(a.ncases, a.hwd))) != MRIRT_OK) return rc;
     a.chunkSums = (uint32_t*)scratch; a.offsets = offsets; a.index = index;
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(tum_chunk_kernel, dim3(a.chunks, a.ncases), dim3(kTumThreads), 0, s, a);

@@ -8,6 +8,7 @@
 //   muon_apply_kernel      W <- W - lr (scale O + wd W)
 // The global-norm clip factor and the biases' AdamW are csrc/inr_optim.hip's own kernels (opt_norm_and_bias_step).
 // No allocation, no host synchronisation, no float atomics, no workgroup waits for another: the same inputs give the same bits.
+#include "inr_device.h"
 #include "inr_gemm.h"
 #include "inr_muon.h"
 #include "mrirt_host.h"
@@ -55,12 +56,6 @@ __global__ __launch_bounds__(kTrThreads) void muon_gemm_kernel(MuonNsArgs a) {
     }
 }
 
-__device__ __forceinline__ double muon_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-
 // block l: thread t adds the squares of elements t, t + kMuonThreads, ... of layer l; the 64 lanes of a wave fold by halves,
 // the four wave sums add in wave order
 __global__ __launch_bounds__(kMuonThreads) void muon_norm_kernel(MuonPlan plan, const float* m, double eps, double* denom) {
@@ -70,7 +65,7 @@ __global__ __launch_bounds__(kMuonThreads) void muon_norm_kernel(MuonPlan plan, 
     const int64_t n = (int64_t)y.in * y.out;
     double acc = 0.0;
     for (int64_t i = threadIdx.x; i < n; i += kMuonThreads) acc += (double)p[i] * (double)p[i];
-    const double s = muon_wave_sum(acc);
+    const double s = wave_sum(acc);
     if ((threadIdx.x & 63u) == 0) part[threadIdx.x >> 6] = s;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -137,12 +132,6 @@ static int muon_desc(const MrirtInrDesc* d, MuonPlan& P, MuonLayout& L) {
     return MRIRT_OK;
 }
 
-static int check_muon_scratch(const void* scratch, int64_t have, uint64_t need) {
-    if (!scratch) return MRIRT_ERR_NULL;
-    if (((uintptr_t)scratch & 15u) != 0 || have < 0 || (uint64_t)have < need) return MRIRT_ERR_ARG;
-    return MRIRT_OK;
-}
-
 static uint32_t elem_blocks(uint64_t n) { return (uint32_t)((n + kMuonThreads - 1) / kMuonThreads); }
 
 // m -> out through the Newton-Schulz part of the scratch; every argument has been checked
@@ -190,7 +179,7 @@ extern "C" int mrirt_muon_orthogonalize(const MrirtInrDesc* desc, const float* m
     int rc = muon_desc(desc, P, L);
     if (rc != MRIRT_OK) return rc;
     if ((rc = check_muon(hp)) != MRIRT_OK) return rc;
-    if ((rc = check_muon_scratch(scratch, scratch_bytes, L.bytes)) != MRIRT_OK) return rc;
+    if ((rc = check_scratch(scratch, scratch_bytes, L.bytes)) != MRIRT_OK) return rc;
     return newton_schulz(P, L, m_flat, out_flat, hp, (char*)scratch, (hipStream_t)stream);
 }
 
@@ -205,7 +194,7 @@ extern "C" int mrirt_muon_step(const MrirtInrDesc* desc, float* w, float* b, con
     if ((rc = check_muon(hp)) != MRIRT_OK) return rc;
     if ((rc = opt_check_adamw(adamw, true)) != MRIRT_OK) return rc;
     if (!isfinite(gscale) || ((uintptr_t)gnorm & 7u) != 0) return MRIRT_ERR_ARG;
-    if ((rc = check_muon_scratch(scratch, scratch_bytes, L.bytes)) != MRIRT_OK) return rc;
+    if ((rc = check_scratch(scratch, scratch_bytes, L.bytes)) != MRIRT_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     char* base = (char*)scratch;
     // the clip factor over all gradients and the biases' AdamW: mrirt_inr_adamw_step's own kernels

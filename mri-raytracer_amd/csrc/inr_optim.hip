@@ -9,7 +9,7 @@
 //   mrirt_inr_train_run_muon  the same run with mrirt_muon_step (csrc/inr_muon.hip) as the update; that step borrows the norm
 //                          pass and the bias update from here (opt_norm_and_bias_step)
 // No float atomics and no data-dependent order anywhere: the same inputs give the same bits.
-#include "inr_optim.h"
+#include "inr_device.h"
 #include "mrirt_host.h"
 
 namespace mrirt {
@@ -32,15 +32,7 @@ __global__ __launch_bounds__(kOptThreads) void sample_kernel(SampleArgs a) {
     const int64_t i = (int64_t)blockIdx.x * kOptThreads + threadIdx.x;
     if (i >= a.n) return;
     const SamplePoint p = sample_point(a.seed, a.batch, (uint32_t)i, a.ncases, a.H, a.W, a.D);
-    const int64_t v = voxel_offset(p.x, p.y, p.z, a.W, a.D);
-    a.coords[3 * i + 0] = sample_coord(p.x, a.H);
-    a.coords[3 * i + 1] = sample_coord(p.y, a.W);
-    a.coords[3 * i + 2] = sample_coord(p.z, a.D);
-    a.labels[i] = (int32_t)a.seg[p.cs][v];
-    if (a.M) {
-        const float* m = a.mods[p.cs];
-        for (uint32_t k = 0; k < a.M; ++k) a.feats[i * a.M + k] = m[mod_offset(k, v, a.hwd)];
-    }
+    sample_write(i, p, a.mods, a.seg, a.M, a.H, a.W, a.D, a.hwd, a.coords, a.feats, a.labels);
 }
 
 struct OptArgs {
@@ -55,12 +47,6 @@ struct OptArgs {
     double* gnorm;               // [0] norm, [1] s
 };
 
-__device__ __forceinline__ double opt_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-
 __global__ __launch_bounds__(kOptThreads) void sqnorm_partial_kernel(OptArgs a) {
     __shared__ double part[kOptThreads / 64];
     const int64_t n = a.nw + a.nb;
@@ -69,7 +55,7 @@ __global__ __launch_bounds__(kOptThreads) void sqnorm_partial_kernel(OptArgs a) 
         const float g = (i < a.nw ? a.gw[i] : a.gb[i - a.nw]) * a.gscale;
         acc += (double)g * (double)g;
     }
-    const double s = opt_wave_sum(acc);
+    const double s = wave_sum(acc);
     if ((threadIdx.x & 63u) == 0) part[threadIdx.x >> 6] = s;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -142,12 +128,6 @@ static int check_adamw(const MrirtAdamW* hp, bool needLr) {
     if ((needLr && !finite_f(hp->lr)) || !finite_f(hp->b1) || !finite_f(hp->b2) || !finite_f(hp->eps) || !finite_f(hp->weightDecay)) return MRIRT_ERR_ARG;
     if (hp->b1 < 0.0f || hp->b1 >= 1.0f || hp->b2 < 0.0f || hp->b2 >= 1.0f || !(hp->eps > 0.0f)) return MRIRT_ERR_ARG;
     if (hp->clipNorm != hp->clipNorm || hp->clipNorm == -INFINITY) return MRIRT_ERR_ARG;
-    return MRIRT_OK;
-}
-
-static int check_opt_scratch(const void* scratch, int64_t have, uint64_t need) {
-    if (!scratch) return MRIRT_ERR_NULL;
-    if (((uintptr_t)scratch & 15u) != 0 || have < 0 || (uint64_t)have < need) return MRIRT_ERR_ARG;
     return MRIRT_OK;
 }
 
@@ -254,7 +234,7 @@ extern "C" int mrirt_inr_adamw_step(float* w, float* b, const float* gw, const f
     int rc = check_adamw(hp, true);
     if (rc != MRIRT_OK) return rc;
     if (!isfinite(gscale) || ((uintptr_t)gnorm & 7u) != 0) return MRIRT_ERR_ARG;
-    if ((rc = check_opt_scratch(scratch, scratch_bytes, opt_scratch_bytes(nw + nb))) != MRIRT_OK) return rc;
+    if ((rc = check_scratch(scratch, scratch_bytes, opt_scratch_bytes(nw + nb))) != MRIRT_OK) return rc;
     const OptArgs a = opt_args(w, b, gw, gb, mu_w, mu_b, nu_w, nu_b, nw, nb, nw, hp, t, gscale, gnorm, scratch);
     if ((rc = launch_norm(a, (hipStream_t)stream)) != MRIRT_OK) return rc;
     return launch_adamw(a, (hipStream_t)stream);
@@ -334,7 +314,7 @@ static int train_run(const MrirtInrDesc* desc, bool siren, const MrirtInrCache* 
     const MrirtInrLossExt* lossExt = extras ? extras->loss : nullptr;
     const bool mix = extras && extras->nTumour > 0;
     const int64_t lossBytes = lossExt ? mrirt_inr_loss_ext_scratch_bytes(cfg->microBatch) : 0;
-    if ((rc = check_opt_scratch(scratch, scratch_bytes, R.bytes + (uint64_t)muonBytes + (uint64_t)lossBytes)) != MRIRT_OK) return rc;
+    if ((rc = check_scratch(scratch, scratch_bytes, R.bytes + (uint64_t)muonBytes + (uint64_t)lossBytes)) != MRIRT_OK) return rc;
     const int64_t n = cfg->microBatch;
     const uint32_t C = desc->outDim;
     char* base = (char*)scratch;

@@ -7,42 +7,21 @@
 //   forward   inputs x (Fourier features as the inference path builds them) -> per layer H . W + b, ReLU -> saved h_l
 //   loss      per-point softmax / CE and per-block fp64 class sums -> totals, loss, aux -> dlogits
 //   backward  per layer: H^T . dZ over split-n slabs (db as the row of ones) -> fixed-order slab sum; dZ . W^T, masked
-// The three products are one LDS-tiled GEMM template; its index arithmetic lives in inr_train.h.  No float atomics: every sum
+// The three products are one LDS-tiled GEMM template; its index arithmetic lives in inr_train.h, its staging in inr_gemm.h,
+// the wave sum and the softmax it shares with the other training kernels in inr_device.h.  No float atomics: every sum
 // over the batch has a fixed order, so two runs on the same inputs give the same bits.
 //
 // SIREN kinds run the same pipeline through entry points of their own (mrirt_siren_*): the inputs are
 // scaled by w0, the hidden layers' epilogue takes the STRICT sine of siren_sincos.h and saves the cosine beside it, and the
 // backward multiplies by that cosine where the ReLU step masks.
-#include "inr_train.h"
+#include "inr_device.h"
+#include "inr_gemm.h"
 #include "siren_sincos.h"
 #include "mrirt_host.h"
 
 namespace mrirt {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 enum { kEpiBias = 0, kEpiMask = 1, kEpiSlab = 2, kEpiSine = 3, kEpiCos = 4 };
-
-template <int R, bool KFAST>
-__device__ __forceinline__ void tr_fetch(const TrView& v, uint32_t non0, int64_t k0, int64_t kEnd, float (&reg)[R / 16]) {
-#pragma unroll
-    for (int i = 0; i < R / 16; ++i) {
-        uint32_t r, k;
-        tr_stage_coord<R, KFAST>(threadIdx.x, i, r, k);
-        const int64_t off = tr_view_offset(v, non0 + r, k0 + k, kEnd);
-        reg[i] = off >= 0 ? v.p[off] : (off == -2 ? 1.0f : 0.0f);
-    }
-}
-
-template <int R, bool KFAST>
-__device__ __forceinline__ void tr_stage(float* lds, const float (&reg)[R / 16]) {
-#pragma unroll
-    for (int i = 0; i < R / 16; ++i) {
-        uint32_t r, k;
-        tr_stage_coord<R, KFAST>(threadIdx.x, i, r, k);
-        lds[k * TrLds<R>::pitch + r] = reg[i];
-    }
-}
 
 template <int BN, bool AKFAST, bool BKFAST, int EPI>
 __global__ __launch_bounds__(kTrThreads) void tr_gemm_kernel(TrGemmArgs a) {
@@ -54,20 +33,20 @@ __global__ __launch_bounds__(kTrThreads) void tr_gemm_kernel(TrGemmArgs a) {
     int64_t kBegin = 0, kEnd = a.K;
     if (EPI == kEpiSlab) tr_slab_range(a.K, a.slabLen, blockIdx.z, kBegin, kEnd);
 
-    f32x4 acc[NT];
+    f32x4 acc[NT];                                       // gm_accumulate's loop, kept here: see inr_gemm.h
 #pragma unroll
     for (int j = 0; j < NT; ++j) acc[j] = f32x4{ 0.0f, 0.0f, 0.0f, 0.0f };
     float ra[kTrBM / 16], rb[BN / 16];
-    tr_fetch<kTrBM, AKFAST>(a.A, m0, kBegin, kEnd, ra);
-    tr_fetch<BN, BKFAST>(a.B, n0, kBegin, kEnd, rb);
+    gm_fetch<kTrBM, AKFAST>(a.A, m0, kBegin, kEnd, ra);
+    gm_fetch<BN, BKFAST>(a.B, n0, kBegin, kEnd, rb);
     for (int64_t k0 = kBegin; k0 < kEnd; k0 += kTrBK) {
         __syncthreads();                                 // the previous tile's reads are done
-        tr_stage<kTrBM, AKFAST>(As, ra);
-        tr_stage<BN, BKFAST>(Bs, rb);
+        gm_stage<kTrBM, AKFAST>(As, ra);
+        gm_stage<BN, BKFAST>(Bs, rb);
         __syncthreads();
         if (k0 + kTrBK < kEnd) {                         // the next tile's loads fly under this tile's MFMAs
-            tr_fetch<kTrBM, AKFAST>(a.A, m0, k0 + kTrBK, kEnd, ra);
-            tr_fetch<BN, BKFAST>(a.B, n0, k0 + kTrBK, kEnd, rb);
+            gm_fetch<kTrBM, AKFAST>(a.A, m0, k0 + kTrBK, kEnd, ra);
+            gm_fetch<BN, BKFAST>(a.B, n0, k0 + kTrBK, kEnd, rb);
         }
 #pragma unroll
         for (int s = 0; s < kTrBK / 4; ++s) {
@@ -183,31 +162,11 @@ struct LossArgs {
     float* dlogits;
 };
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-
-// softmax of one point: p[k] (fp32), the cross entropy -log p[label] (0 for a label outside 0..C-1)
-__device__ __forceinline__ float point_softmax(const float* z, uint32_t C, int32_t label, float (&p)[kLossMaxClasses]) {
-    float m = z[0];
-    for (uint32_t k = 1; k < C; ++k) m = fmaxf(m, z[k]);
-    float s = 0.0f, zl = 0.0f;
-#pragma unroll
-    for (uint32_t k = 0; k < kLossMaxClasses; ++k) {
-        p[k] = 0.0f;
-        if (k < C) {
-            const float d = z[k] - m;
-            p[k] = expf(d);
-            s += p[k];
-            if ((int32_t)k == label) zl = d;
-        }
-    }
-    const float inv = 1.0f / s;
-#pragma unroll
-    for (uint32_t k = 0; k < kLossMaxClasses; ++k) p[k] *= inv;
-    return (label >= 0 && (uint32_t)label < C) ? logf(s) - zl : 0.0f;
+// the softmax of one point and its cross entropy -log p[label] (0 for a label outside 0..C-1)
+__device__ __forceinline__ float point_ce(const float* z, uint32_t C, int32_t label, float (&p)[kLossMaxClasses]) {
+    float d[kLossMaxClasses], dl;
+    const float s = point_softmax<true>(z, C, label, p, d, dl);
+    return (label >= 0 && (uint32_t)label < C) ? logf(s) - dl : 0.0f;
 }
 
 __global__ __launch_bounds__(kLossThreads) void loss_partial_kernel(LossArgs a) {
@@ -218,7 +177,7 @@ __global__ __launch_bounds__(kLossThreads) void loss_partial_kernel(LossArgs a) 
     for (int64_t i = (int64_t)blockIdx.x * kLossThreads + threadIdx.x; i < a.n; i += (int64_t)a.blocks * kLossThreads) {
         float p[kLossMaxClasses];
         const int32_t label = a.labels[i];
-        const float ce = point_softmax(a.logits + i * a.C, a.C, label, p);
+        const float ce = point_ce(a.logits + i * a.C, a.C, label, p);
         float w = 0.0f;
 #pragma unroll
         for (uint32_t k = 0; k < kLossMaxClasses; ++k) {
@@ -292,7 +251,7 @@ __global__ __launch_bounds__(kLossThreads) void loss_grad_kernel(LossArgs a) {
     if (i >= a.n) return;
     float p[kLossMaxClasses];
     const int32_t label = a.labels[i];
-    point_softmax(a.logits + i * a.C, a.C, label, p);
+    point_ce(a.logits + i * a.C, a.C, label, p);
     float w = 0.0f, dot = 0.0f;
 #pragma unroll
     for (uint32_t k = 0; k < kLossMaxClasses; ++k) {
@@ -325,12 +284,6 @@ static int train_desc(const MrirtInrDesc* d, int64_t n, bool siren, TrainLayout&
     S = siren_layout(d->numLayers, d->inDim, d->hidden, d->outDim, n);
     L = S.T;
     if (siren) L.bytes = S.bytes;
-    return MRIRT_OK;
-}
-
-static int check_scratch(const void* scratch, int64_t have, uint64_t need) {
-    if (!scratch) return MRIRT_ERR_NULL;
-    if (((uintptr_t)scratch & 15u) != 0 || have < 0 || (uint64_t)have < need) return MRIRT_ERR_ARG;
     return MRIRT_OK;
 }
 

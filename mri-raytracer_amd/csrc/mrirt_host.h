@@ -203,6 +203,13 @@ inline void fill_label_addr(LabelAddr& a, const uint32_t dims[3], uint32_t layou
     }
 }
 
+// the scratch buffer of an INR training entry point: non-null, 16-byte aligned, at least `need` of its `have` bytes
+inline int check_scratch(const void* scratch, int64_t have, uint64_t need) {
+    if (!scratch) return MRIRT_ERR_NULL;
+    if (((uintptr_t)scratch & 15u) != 0 || have < 0 || (uint64_t)have < need) return MRIRT_ERR_ARG;
+    return MRIRT_OK;
+}
+
 // csrc/inr_optim.hip, for the other optimiser built on its kernels (csrc/inr_muon.hip): the AdamW hyper-parameter check of
 // mrirt_inr_adamw_step, and its norm pass over [gw | gb] (gnorm[0] = norm, gnorm[1] = clip factor) followed by its update
 // kernel on the biases alone.  scratch: opt_scratch_bytes(nw + nb) bytes; nothing is checked here.

@@ -457,18 +457,21 @@ def labels_for_viewer(pred_hwd: torch.Tensor) -> torch.Tensor:
 
 
 # --- training step: fp32 forward, loss and weight gradients (csrc/inr_train.hip) ------------------------------------------------
-def train_desc(dims: Sequence[int], fourier_freqs: Optional[int] = None, num_mods: int = 0) -> _lib.InrDesc:
-    """Descriptor of a ReLU network ``dims = [in, hidden, .., hidden, out]`` for the fp32 training entry points:
-    ``fourier_freqs=None`` is the raw kind (the input matrix is given), otherwise the Fourier kind over ``num_mods``
-    intensities.  The packed inference images (``desc.weights`` / ``desc.biases``) stay unset: nothing here reads them."""
+def _step_desc(dims: Sequence[int], kind: int, fourier_freqs: int, num_mods: int, w0: float = 0.0) -> _lib.InrDesc:
     dims = [int(v) for v in dims]
     if len(dims) < 3 or any(v != dims[1] for v in dims[1:-1]):
         raise ValueError(f"layer widths {dims}: the kernels need at least one hidden layer and equal hidden widths")
     d = _lib.InrDesc()
-    d.kind = KIND_RAW_RELU if fourier_freqs is None else KIND_FOURIER_RELU
-    d.numLayers, d.inDim, d.hidden, d.outDim = len(dims) - 1, dims[0], dims[1], dims[-1]
-    d.fourierFreqs, d.numMods = (0, 0) if fourier_freqs is None else (int(fourier_freqs), int(num_mods))
+    d.kind, d.numLayers, d.inDim, d.hidden, d.outDim = kind, len(dims) - 1, dims[0], dims[1], dims[-1]
+    d.fourierFreqs, d.numMods, d.w0 = int(fourier_freqs), int(num_mods), float(w0)
     return d
+
+
+def train_desc(dims: Sequence[int], fourier_freqs: Optional[int] = None, num_mods: int = 0) -> _lib.InrDesc:
+    """Descriptor of a ReLU network ``dims = [in, hidden, .., hidden, out]`` for the fp32 training entry points:
+    ``fourier_freqs=None`` is the raw kind (the input matrix is given), otherwise the Fourier kind over ``num_mods``
+    intensities.  The packed inference images (``desc.weights`` / ``desc.biases``) stay unset: nothing here reads them."""
+    return _step_desc(dims, KIND_RAW_RELU, 0, 0) if fourier_freqs is None else _step_desc(dims, KIND_FOURIER_RELU, fourier_freqs, num_mods)
 
 
 def _param_dims(Ws, bs) -> List[int]:
@@ -479,21 +482,57 @@ def _param_dims(Ws, bs) -> List[int]:
     return dims
 
 
-def train_scratch(desc: _lib.InrDesc, n: int, dev) -> torch.Tensor:
-    nbytes = int(_lib.lib().mrirt_inr_train_scratch_bytes(C.byref(desc), int(n)))
+# mrirt_inr_* takes the ReLU kinds, mrirt_siren_* the SIREN kinds.  The public twins name their family, so the library still
+# refuses a descriptor of the other one; the autograd function and the loss closure go by the descriptor's kind.
+_SHAPE_TEXT = {"inr": ("", "ReLU kinds", ""), "siren": ("SIREN ", "SIREN kinds", ", finite w0 != 0")}
+
+
+def _family(desc: _lib.InrDesc) -> str:
+    return "siren" if int(desc.kind) in (KIND_SIREN, KIND_RAW_SIREN) else "inr"
+
+
+def _step_symbol(desc: _lib.InrDesc, job: str, family: Optional[str] = None) -> str:
+    """The C entry point of ``job`` ("train_scratch_bytes", "forward_f32", "backward") for ``family``, or for the descriptor's."""
+    return f"mrirt_{family or _family(desc)}_{job}"
+
+
+def _step_scratch(desc: _lib.InrDesc, n: int, dev, family: Optional[str] = None) -> torch.Tensor:
+    family = family or _family(desc)
+    nbytes = int(getattr(_lib.lib(), _step_symbol(desc, "train_scratch_bytes", family))(C.byref(desc), int(n)))
     if nbytes <= 0:
-        raise ValueError(f"unsupported training shape: in {desc.inDim}, hidden {desc.hidden} x {desc.numLayers - 1}, out {desc.outDim}, "
-                         f"n {n} (ReLU kinds, hidden in {{32,64,128,256}}, in <= 128, out <= 16, <= 8 layers, n >= 1)")
+        what, kinds, more = _SHAPE_TEXT[family]
+        raise ValueError(f"unsupported {what}training shape: in {desc.inDim}, hidden {desc.hidden} x {desc.numLayers - 1}, out {desc.outDim}, "
+                         f"n {n} ({kinds}, hidden in {{32,64,128,256}}, in <= 128, out <= 16, <= 8 layers, n >= 1{more})")
     return torch.empty(nbytes, dtype=torch.uint8, device=dev)
+
+
+def _step_forward(desc, w_flat, b_flat, coords, feats, n, scratch, family=None):
+    name = _step_symbol(desc, "forward_f32", family)
+    logits = torch.empty((int(n), int(desc.outDim)), dtype=torch.float32, device=w_flat.device)
+    rc = getattr(_lib.lib(), name)(C.byref(desc), _ptr(w_flat), _ptr(b_flat), _ptr(coords), _ptr(feats), int(n), _ptr(logits),
+                                   _ptr(scratch), scratch.numel(), _stream_ptr(None))
+    _lib.check(rc, name)
+    return logits
+
+
+def _step_backward(desc, w_flat, n, dlogits, scratch, grad_w=None, grad_b=None, accumulate=False, family=None):
+    name = _step_symbol(desc, "backward", family)
+    nb = int(desc.hidden) * (int(desc.numLayers) - 1) + int(desc.outDim)
+    gw = grad_w if grad_w is not None else torch.empty_like(w_flat)
+    gb = grad_b if grad_b is not None else torch.empty(nb, dtype=torch.float32, device=w_flat.device)
+    rc = getattr(_lib.lib(), name)(C.byref(desc), _ptr(w_flat), int(n), _ptr(dlogits), _ptr(gw), _ptr(gb), 1 if accumulate else 0,
+                                   _ptr(scratch), scratch.numel(), _stream_ptr(None))
+    _lib.check(rc, name)
+    return gw, gb
+
+
+def train_scratch(desc: _lib.InrDesc, n: int, dev) -> torch.Tensor:
+    return _step_scratch(desc, n, dev, "inr")
 
 
 def forward_f32(desc: _lib.InrDesc, w_flat: torch.Tensor, b_flat: torch.Tensor, coords, feats, n: int, scratch: torch.Tensor):
     """``mrirt_inr_forward_f32``: fp32 logits (n, out); the activations the backward pass needs stay in ``scratch``."""
-    logits = torch.empty((int(n), int(desc.outDim)), dtype=torch.float32, device=w_flat.device)
-    rc = _lib.lib().mrirt_inr_forward_f32(C.byref(desc), _ptr(w_flat), _ptr(b_flat), _ptr(coords), _ptr(feats), int(n), _ptr(logits),
-                                          _ptr(scratch), scratch.numel(), _stream_ptr(None))
-    _lib.check(rc, "mrirt_inr_forward_f32")
-    return logits
+    return _step_forward(desc, w_flat, b_flat, coords, feats, n, scratch, "inr")
 
 
 def loss_ext(class_weights, dice_weight: float = 0.0, per_class_dice: bool = False, focal_gamma: float = 0.0, focal_alpha=None,
@@ -565,13 +604,7 @@ def backward_f32(desc: _lib.InrDesc, w_flat: torch.Tensor, n: int, dlogits: torc
                  grad_w: Optional[torch.Tensor] = None, grad_b: Optional[torch.Tensor] = None, accumulate: bool = False):
     """``mrirt_inr_backward``: (grad_w, grad_b) in the flat layouts of the weights / biases, from what ``forward_f32`` left in
     ``scratch``.  ``accumulate`` adds into the given buffers."""
-    nb = int(desc.hidden) * (int(desc.numLayers) - 1) + int(desc.outDim)
-    gw = grad_w if grad_w is not None else torch.empty_like(w_flat)
-    gb = grad_b if grad_b is not None else torch.empty(nb, dtype=torch.float32, device=w_flat.device)
-    rc = _lib.lib().mrirt_inr_backward(C.byref(desc), _ptr(w_flat), int(n), _ptr(dlogits), _ptr(gw), _ptr(gb), 1 if accumulate else 0,
-                                       _ptr(scratch), scratch.numel(), _stream_ptr(None))
-    _lib.check(rc, "mrirt_inr_backward")
-    return gw, gb
+    return _step_backward(desc, w_flat, n, dlogits, scratch, grad_w, grad_b, accumulate, "inr")
 
 
 def _split_grads(gw: torch.Tensor, gb: torch.Tensor, dims: Sequence[int]):
@@ -583,13 +616,8 @@ def _split_grads(gw: torch.Tensor, gb: torch.Tensor, dims: Sequence[int]):
     return out
 
 
-def make_loss_and_grad(num_classes: int, class_weights, dice_weight: float, fourier_freqs: int, ext: Optional[_lib.InrLossExt] = None):
-    """inr/inr/model.py:64-90 on the GPU: returns ``f(params, coords, intensities, labels) -> ((loss, aux), grads)`` with the
-    reference's return shape — ``loss`` a 0-d device tensor, ``aux = {"ce_per_class", "dice_per_class"}`` (device, (C,)),
-    ``grads`` a list of ``{"W", "b"}`` device tensors shaped like ``params`` (NumPy arrays or device tensors);
-    ``intensities`` may be None for a network without modalities.  One fp32
-    forward, the loss and one backward pass (csrc/inr_train.hip); nothing synchronises with the host.  ``ext``
-    (``loss_ext(...)``): the loss is ``mrirt_inr_loss_ext``'s and ``aux`` gains ``"terms"`` (5,)."""
+def _make_step_loss_and_grad(num_classes: int, class_weights, dice_weight: float, ext: Optional[_lib.InrLossExt], make_desc):
+    """The closure of ``make_loss_and_grad`` for either family: ``make_desc(dims, num_mods)`` gives the descriptor."""
     cw = [float(v) for v in np.asarray(class_weights, dtype=np.float32).reshape(-1)]
     if len(cw) != int(num_classes):
         raise ValueError(f"class_weights holds {len(cw)} values for {num_classes} classes")
@@ -604,37 +632,53 @@ def make_loss_and_grad(num_classes: int, class_weights, dice_weight: float, four
         c, f = _dev_f32(coords, dev), (_dev_f32(intensities, dev) if intensities is not None else None)
         n = int(c.shape[0])
         lab = torch.as_tensor(labels).to(dev).to(torch.int32).contiguous()
-        desc = train_desc(dims, fourier_freqs, f.shape[1] if f is not None and f.dim() == 2 else 0)
+        desc = make_desc(dims, f.shape[1] if f is not None and f.dim() == 2 else 0)
         w_flat, b_flat = torch.cat([W.reshape(-1) for W in Ws]), torch.cat(bs)
-        scratch = train_scratch(desc, n, dev)
-        logits = forward_f32(desc, w_flat, b_flat, c, f, n, scratch)
+        scratch = _step_scratch(desc, n, dev)
+        logits = _step_forward(desc, w_flat, b_flat, c, f, n, scratch)
         loss, aux, dl, *terms = loss_and_dlogits(logits, lab, cw, dice_weight, scratch, ext=ext)
-        gw, gb = backward_f32(desc, w_flat, n, dl, scratch)
+        gw, gb = _step_backward(desc, w_flat, n, dl, scratch)
         return (loss, {"ce_per_class": aux[0], "dice_per_class": aux[1], **({"terms": terms[0]} if terms else {})}), _split_grads(gw, gb, dims)
 
     return loss_and_grad
 
 
-class _MlpF32(torch.autograd.Function):
+def make_loss_and_grad(num_classes: int, class_weights, dice_weight: float, fourier_freqs: int, ext: Optional[_lib.InrLossExt] = None):
+    """inr/inr/model.py:64-90 on the GPU: returns ``f(params, coords, intensities, labels) -> ((loss, aux), grads)`` with the
+    reference's return shape — ``loss`` a 0-d device tensor, ``aux = {"ce_per_class", "dice_per_class"}`` (device, (C,)),
+    ``grads`` a list of ``{"W", "b"}`` device tensors shaped like ``params`` (NumPy arrays or device tensors);
+    ``intensities`` may be None for a network without modalities.  One fp32
+    forward, the loss and one backward pass (csrc/inr_train.hip); nothing synchronises with the host.  ``ext``
+    (``loss_ext(...)``): the loss is ``mrirt_inr_loss_ext``'s and ``aux`` gains ``"terms"`` (5,)."""
+    return _make_step_loss_and_grad(num_classes, class_weights, dice_weight, ext, lambda dims, m: train_desc(dims, fourier_freqs, m))
+
+
+class _StepF32(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, coords, feats, fourier_freqs, num_layers, *wb):
+    def forward(ctx, coords, feats, make_desc, num_layers, *wb):
         Ws, bs = wb[:num_layers], wb[num_layers:]
         dims = _param_dims(Ws, bs)
-        dev = Ws[0].device
-        n = int(feats.shape[0]) if fourier_freqs is None else int(coords.shape[0])
-        desc = train_desc(dims, fourier_freqs, 0 if fourier_freqs is None else (feats.shape[1] if feats is not None else 0))
+        desc = make_desc(dims)
+        n = int((feats if int(desc.kind) in (KIND_RAW_RELU, KIND_RAW_SIREN) else coords).shape[0])
         w_flat = torch.cat([W.detach().to(torch.float32).reshape(-1) for W in Ws])
         b_flat = torch.cat([b.detach().to(torch.float32).reshape(-1) for b in bs])
-        scratch = train_scratch(desc, n, dev)
-        logits = forward_f32(desc, w_flat, b_flat, coords, feats, n, scratch)
+        scratch = _step_scratch(desc, n, Ws[0].device)
+        logits = _step_forward(desc, w_flat, b_flat, coords, feats, n, scratch)
         ctx.desc, ctx.dims, ctx.n, ctx.w_flat, ctx.scratch = desc, dims, n, w_flat, scratch
         return logits
 
     @staticmethod
     def backward(ctx, grad_logits):
-        gw, gb = backward_f32(ctx.desc, ctx.w_flat, ctx.n, grad_logits.to(torch.float32).contiguous(), ctx.scratch)
+        gw, gb = _step_backward(ctx.desc, ctx.w_flat, ctx.n, grad_logits.to(torch.float32).contiguous(), ctx.scratch)
         g = _split_grads(gw, gb, ctx.dims)
         return (None, None, None, None, *[x["W"] for x in g], *[x["b"] for x in g])
+
+
+def _step_autograd(Ws, bs, coords, feats, make_desc) -> torch.Tensor:
+    dev = Ws[0].device
+    c = _dev_f32(coords, dev) if coords is not None else None
+    f = _dev_f32(feats, dev) if feats is not None else None
+    return _StepF32.apply(c, f, lambda dims: make_desc(dims, f.shape[1] if f is not None else 0), len(Ws), *Ws, *bs)
 
 
 def mlp_autograd(Ws, bs, coords, feats, fourier_freqs: Optional[int] = None) -> torch.Tensor:
@@ -642,10 +686,7 @@ def mlp_autograd(Ws, bs, coords, feats, fourier_freqs: Optional[int] = None) -> 
     ``mrirt_inr_backward`` — gradients reach ``Ws`` (each (in, out)) and ``bs`` only, so any torch loss and optimiser can fit
     the network.  ``fourier_freqs=None``: ``feats`` is the (n, in) input matrix and ``coords`` is unused; otherwise the
     inputs are built from coords (n, 3) and intensities ``feats`` (n, M) as ``build_input`` does."""
-    dev = Ws[0].device
-    c = _dev_f32(coords, dev) if coords is not None else None
-    f = _dev_f32(feats, dev) if feats is not None else None
-    return _MlpF32.apply(c, f, fourier_freqs, len(Ws), *Ws, *bs)
+    return _step_autograd(Ws, bs, coords, feats, lambda dims, m: train_desc(dims, fourier_freqs, m))
 
 
 # --- training loop: voxel cache + sampler, clipped AdamW, train_inr (csrc/inr_optim.hip) ---------------------------------------
@@ -1132,47 +1173,27 @@ def siren_train_desc(dims: Sequence[int], num_mods: Optional[int] = None, w0: fl
     """Descriptor of a SIREN ``dims = [in, hidden, .., hidden, out]`` for the ``mrirt_siren_*`` entry points: ``num_mods=None``
     is the raw kind (the input matrix is given), otherwise x = (coords, ``num_mods`` intensities) and ``in`` must be
     ``3 + num_mods``."""
-    dims = [int(v) for v in dims]
-    if len(dims) < 3 or any(v != dims[1] for v in dims[1:-1]):
-        raise ValueError(f"layer widths {dims}: the kernels need at least one hidden layer and equal hidden widths")
-    if num_mods is not None and dims[0] != 3 + int(num_mods):
-        raise ValueError(f"a SIREN over {num_mods} modalities has {3 + int(num_mods)} inputs, not {dims[0]}")
+    d = _step_desc(dims, KIND_RAW_SIREN if num_mods is None else KIND_SIREN, 0, 0 if num_mods is None else num_mods, w0)
+    if num_mods is not None and d.inDim != 3 + int(num_mods):
+        raise ValueError(f"a SIREN over {num_mods} modalities has {3 + int(num_mods)} inputs, not {d.inDim}")
     if not np.isfinite(w0) or float(w0) == 0.0:
         raise ValueError("w0 must be finite and non-zero")
-    d = _lib.InrDesc()
-    d.kind = KIND_RAW_SIREN if num_mods is None else KIND_SIREN
-    d.numLayers, d.inDim, d.hidden, d.outDim = len(dims) - 1, dims[0], dims[1], dims[-1]
-    d.fourierFreqs, d.numMods, d.w0 = 0, (0 if num_mods is None else int(num_mods)), float(w0)
     return d
 
 
 def siren_train_scratch(desc: _lib.InrDesc, n: int, dev) -> torch.Tensor:
-    nbytes = int(_lib.lib().mrirt_siren_train_scratch_bytes(C.byref(desc), int(n)))
-    if nbytes <= 0:
-        raise ValueError(f"unsupported SIREN training shape: in {desc.inDim}, hidden {desc.hidden} x {desc.numLayers - 1}, out {desc.outDim}, "
-                         f"n {n} (SIREN kinds, hidden in {{32,64,128,256}}, in <= 128, out <= 16, <= 8 layers, n >= 1, finite w0 != 0)")
-    return torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    return _step_scratch(desc, n, dev, "siren")
 
 
 def siren_forward_f32(desc: _lib.InrDesc, w_flat: torch.Tensor, b_flat: torch.Tensor, coords, feats, n: int, scratch: torch.Tensor):
     """``mrirt_siren_forward_f32``: fp32 logits (n, out); inputs, sines and cosines stay in ``scratch`` for the backward."""
-    logits = torch.empty((int(n), int(desc.outDim)), dtype=torch.float32, device=w_flat.device)
-    rc = _lib.lib().mrirt_siren_forward_f32(C.byref(desc), _ptr(w_flat), _ptr(b_flat), _ptr(coords), _ptr(feats), int(n), _ptr(logits),
-                                            _ptr(scratch), scratch.numel(), _stream_ptr(None))
-    _lib.check(rc, "mrirt_siren_forward_f32")
-    return logits
+    return _step_forward(desc, w_flat, b_flat, coords, feats, n, scratch, "siren")
 
 
 def siren_backward_f32(desc: _lib.InrDesc, w_flat: torch.Tensor, n: int, dlogits: torch.Tensor, scratch: torch.Tensor,
                        grad_w: Optional[torch.Tensor] = None, grad_b: Optional[torch.Tensor] = None, accumulate: bool = False):
     """``mrirt_siren_backward``: (grad_w, grad_b) in the flat layouts, from what ``siren_forward_f32`` left in ``scratch``."""
-    nb = int(desc.hidden) * (int(desc.numLayers) - 1) + int(desc.outDim)
-    gw = grad_w if grad_w is not None else torch.empty_like(w_flat)
-    gb = grad_b if grad_b is not None else torch.empty(nb, dtype=torch.float32, device=w_flat.device)
-    rc = _lib.lib().mrirt_siren_backward(C.byref(desc), _ptr(w_flat), int(n), _ptr(dlogits), _ptr(gw), _ptr(gb), 1 if accumulate else 0,
-                                         _ptr(scratch), scratch.numel(), _stream_ptr(None))
-    _lib.check(rc, "mrirt_siren_backward")
-    return gw, gb
+    return _step_backward(desc, w_flat, n, dlogits, scratch, grad_w, grad_b, accumulate, "siren")
 
 
 def _siren_dict(layers) -> Dict[str, Dict[str, Any]]:
@@ -1183,62 +1204,21 @@ def make_siren_loss_and_grad(num_classes: int, class_weights, dice_weight: float
     """``make_loss_and_grad`` for the notebook's SIREN: ``f(params, coords, intensities, labels) -> ((loss, aux), grads)`` with
     ``params`` the dict ``l{i} -> {"w", "b"}`` and ``grads`` a dict of device tensors shaped like it.  x = (coords, intensities).
     ``ext`` as in ``make_loss_and_grad``."""
-    cw = [float(v) for v in np.asarray(class_weights, dtype=np.float32).reshape(-1)]
-    if len(cw) != int(num_classes):
-        raise ValueError(f"class_weights holds {len(cw)} values for {num_classes} classes")
+    f = _make_step_loss_and_grad(num_classes, class_weights, dice_weight, ext, lambda dims, m: siren_train_desc(dims, m, w0))
 
     def loss_and_grad(params, coords, intensities, labels):
-        dev = _require_gpu()
-        layers = [(params[f"l{i}"]["w"], params[f"l{i}"]["b"]) for i in range(len(params))]
-        Ws, bs = [_dev_f32(W, dev) for W, _ in layers], [_dev_f32(b, dev) for _, b in layers]
-        dims = _param_dims(Ws, bs)
-        if dims[-1] != int(num_classes):
-            raise ValueError(f"the network has {dims[-1]} outputs for {num_classes} classes")
-        c, f = _dev_f32(coords, dev), (_dev_f32(intensities, dev) if intensities is not None else None)
-        n = int(c.shape[0])
-        lab = torch.as_tensor(labels).to(dev).to(torch.int32).contiguous()
-        desc = siren_train_desc(dims, f.shape[1] if f is not None and f.dim() == 2 else 0, w0)
-        w_flat, b_flat = torch.cat([W.reshape(-1) for W in Ws]), torch.cat(bs)
-        scratch = siren_train_scratch(desc, n, dev)
-        logits = siren_forward_f32(desc, w_flat, b_flat, c, f, n, scratch)
-        loss, aux, dl, *terms = loss_and_dlogits(logits, lab, cw, dice_weight, scratch, ext=ext)
-        gw, gb = siren_backward_f32(desc, w_flat, n, dl, scratch)
-        return (loss, {"ce_per_class": aux[0], "dice_per_class": aux[1], **({"terms": terms[0]} if terms else {})}), _siren_dict(_split_grads(gw, gb, dims))
+        layers = [{"W": params[f"l{i}"]["w"], "b": params[f"l{i}"]["b"]} for i in range(len(params))]
+        out, grads = f(layers, coords, intensities, labels)
+        return out, _siren_dict(grads)
 
     return loss_and_grad
-
-
-class _SirenF32(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, coords, feats, w0, num_layers, *wb):
-        Ws, bs = wb[:num_layers], wb[num_layers:]
-        dims = _param_dims(Ws, bs)
-        dev = Ws[0].device
-        raw = coords is None
-        n = int(feats.shape[0]) if raw else int(coords.shape[0])
-        desc = siren_train_desc(dims, None if raw else (feats.shape[1] if feats is not None else 0), w0)
-        w_flat = torch.cat([W.detach().to(torch.float32).reshape(-1) for W in Ws])
-        b_flat = torch.cat([b.detach().to(torch.float32).reshape(-1) for b in bs])
-        scratch = siren_train_scratch(desc, n, dev)
-        logits = siren_forward_f32(desc, w_flat, b_flat, coords, feats, n, scratch)
-        ctx.desc, ctx.dims, ctx.n, ctx.w_flat, ctx.scratch = desc, dims, n, w_flat, scratch
-        return logits
-
-    @staticmethod
-    def backward(ctx, grad_logits):
-        gw, gb = siren_backward_f32(ctx.desc, ctx.w_flat, ctx.n, grad_logits.to(torch.float32).contiguous(), ctx.scratch)
-        g = _split_grads(gw, gb, ctx.dims)
-        return (None, None, None, None, *[x["W"] for x in g], *[x["b"] for x in g])
 
 
 def siren_autograd(ws, bs, coords, feats, w0: float = 30.0) -> torch.Tensor:
     """Differentiable fp32 logits (n, out) of a SIREN: forward ``mrirt_siren_forward_f32``, backward ``mrirt_siren_backward``;
     gradients reach ``ws`` (each (in, out)) and ``bs`` only.  ``coords=None``: ``feats`` is the (n, in) input matrix; otherwise
     x = (coords (n, 3), intensities ``feats`` (n, M))."""
-    dev = ws[0].device
-    c = _dev_f32(coords, dev) if coords is not None else None
-    f = _dev_f32(feats, dev) if feats is not None else None
-    return _SirenF32.apply(c, f, float(w0), len(ws), *ws, *bs)
+    return _step_autograd(ws, bs, coords, feats, lambda dims, m: siren_train_desc(dims, None if coords is None else m, float(w0)))
 
 
 def train_siren(config: Dict[str, Any], cases_or_cache, val_cases=None, params=None, resume_from=None, log=None, save_path=None):
