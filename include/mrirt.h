@@ -32,6 +32,8 @@ extern "C" {
  *    ray tracer), mrirt_sizeof(6); mrirt_edt_scratch_bytes, mrirt_edt_squared, mrirt_hausdorff (no new struct);
  *    mrirt_surface_scratch_bytes, mrirt_surface_count, mrirt_surface_extract (no new struct);
  *    mrirt_render_brats_backward (the K1 backward pass on LINEAR grids; no new struct);
+ *    mrirt_render_brats_soft, mrirt_render_brats_soft_backward (the soft prediction overlay and its gradient to the
+ *    per-sample logits; no new struct);
  *    the INR training loop: MrirtInrCache, MrirtAdamW, MrirtInrTrainCfg, MrirtInrTrainState (mrirt_sizeof(7..10)),
  *    mrirt_inr_sample_batch, mrirt_inr_adamw_scratch_bytes, mrirt_inr_adamw_step, mrirt_inr_lr_schedule,
  *    mrirt_inr_train_run_scratch_bytes, mrirt_inr_train_run;
@@ -768,6 +770,52 @@ int mrirt_render_brats_backward(const MrirtBratsParams* params, const MrirtRende
                                 const float* const vol[4], const uint32_t* labels, const uint32_t* preds,
                                 const float* grad_rgba, int64_t grad_pitch_px,
                                 float* const grad_vol[4], double* grad_tf, void* stream);
+
+/* ------------------------------------------------------------------------------------ */
+/* Soft prediction overlay: a differentiable INR render (frame gradients to the logits)  */
+/* ------------------------------------------------------------------------------------ */
+/* The frame is K1's (brats_rt.slang:85-168) on LINEAR fp32 grids (whole image, shadeMode 0, either camera mode) with the
+ * third event of each step, the prediction overlay of :154-162, replaced by a SOFT event that the sample's class
+ * probabilities drive.  The forward's own STRICT fp32 values are constants of the frame: ray set-up, t0 / t1, the sample
+ * positions, cells and trilinear weights, the intensity event and the ground-truth overlay event (setup_ray, locate,
+ * Taps<0, false>, composite with Labels{seg, 0}).  params->showPred is ignored: the soft event takes that overlay's place.
+ * The soft event of sample k of ray p (p = y * width + x):
+ *   z = logits[offsets[p] + k][0 .. C)    its logits row (fp32, 1 <= C = num_classes <= 16; rows are C floats apart); the
+ *                                         numbering is that of mrirt_brats_sample_counts / mrirt_brats_emit_samples, and the
+ *                                         caller vouches that every row offsets[p] .. offsets[p] + counts[p] - 1 exists
+ *   Kc = min(C, 8),  D = stepSize * 1.5,  w_k = lutColorAlpha[k].w,  rgb_k = lutColorAlpha[k].rgb
+ *   p = softmax(z) over all C classes
+ *   sigma = sum_{k=1..Kc-1} p_k w_k        E = sum_{k=1..Kc-1} p_k w_k rgb_k
+ *   sigma > 0:  alpha = 1 - exp(-sigma D),  c = E / sigma    evaluated in fp64 from the fp32 logits, each rounded ONCE to fp32,
+ *               then applied exactly like a label event:  at = alpha T;  C += at c;  T *= (1 - alpha)   (fp32)
+ *   sigma <= 0: no event (every LUT opacity zero, C == 1, the softmax underflowed onto class 0).  Classes >= 8 carry
+ *               probability mass but draw nothing, as labels >= 8 do in the shader.
+ * One-hot probabilities on class l reproduce the hard event of the shader: c == rgb_l exactly, alpha up to the rounding of
+ * the fp32 against the fp64 argument of exp.  The loop condition `t < t1 && T > ert` is tested before every step on the fp32
+ * state, as in the forward; early termination is a discrete decision and carries no gradient.
+ *   stats_dev: optional, ONE device uint64 counter, atomically incremented by the composited samples (steps taken).
+ * Backward, with G = dL/dC per pixel (grad_rgba: device fp32 RGBA, 16-byte aligned, grad_pitch_px pixels per row, alpha
+ * ignored), T the transmittance in front of a soft event and R = C_final - C_after that event (what all later events add):
+ *   dL/dalpha = T (G . c) - (G . R) / (1 - alpha)
+ *   dL/dc     = T alpha G
+ *   dL/dp_k   = w_k [ dL/dalpha D (1 - alpha) + T alpha G . (rgb_k - c) / sigma ]   for 1 <= k < Kc; 0 for k = 0 and k >= 8
+ *   dlogits_j = p_j (dL/dp_j - sum_k p_k dL/dp_k)
+ * in fp64 (csrc/brats_soft.h), stored as fp32.  Every row offsets[p] .. offsets[p] + counts[p] - 1 is written with `=`, not
+ * `+=`; exact zeros: rows of steps not taken after termination, rows with sigma <= 0, rows of rays whose G is zero in all
+ * three channels.  Rays that miss the box own no rows; rows no ray owns are not touched.  Each row has one writer and there
+ * are no atomics: the same inputs give the same bits.  Not differentiated: camera, stepSize, the LUT, voxels and transfer
+ * function (mrirt_render_brats_backward is for the last two); intensity and ground-truth events are fixed occluders.
+ * Checks (before any HIP call): those of every K1 entry point, and
+ *   MRIRT_ERR_NULL    logits, offsets, out_rgba / grad_rgba or dlogits is NULL
+ *   MRIRT_ERR_LAYOUT  ext->layout or ext->labelLayout other than MRIRT_LAYOUT_LINEAR
+ *   MRIRT_ERR_ARG     shadeMode != 0, tile sharding, outFormat != MRIRT_OUT_RGBA32F, math != MRIRT_MATH_STRICT, num_classes
+ *                     outside 1..16, lutColorAlpha[k].w negative or not finite for a k in 1..7 */
+int mrirt_render_brats_soft(const MrirtBratsParams* params, const MrirtRenderExt* ext, const float* const vol[4],
+                            const uint32_t* labels, const float* logits, uint32_t num_classes, const int64_t* offsets,
+                            float* out_rgba, int64_t pitch_px, uint64_t* stats_dev, void* stream);
+int mrirt_render_brats_soft_backward(const MrirtBratsParams* params, const MrirtRenderExt* ext, const float* const vol[4],
+                                     const uint32_t* labels, const float* logits, uint32_t num_classes, const int64_t* offsets,
+                                     const float* grad_rgba, int64_t grad_pitch_px, float* dlogits, void* stream);
 
 /* ------------------------------------------------------------------------------------ */
 /* Per-sample INR render, one call (BASELINE config 5)                                   */

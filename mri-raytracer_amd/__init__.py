@@ -6,6 +6,7 @@ the task-mandated name ``mri-raytracer_amd``.  Layout:
   _lib.py     ctypes binding (fails loudly when the library is missing — no CPU fallback)
   render.py   render_brats / render_volume_u8 / render_sdf over device tensors
   grad.py     K1 backward: render_brats_backward, render_brats_autograd (frame gradients to voxels and window / level)
+  soft.py     the soft prediction overlay: render_brats_soft, its backward and render_brats_soft_autograd (frame gradients to logits)
   mesh.py     K4: PLY loading, the reference's BVH, upload + validation, render_mesh; class surfaces of label volumes
   shim.py     slangpy-shaped ``Device`` / ``ComputeKernel.dispatch(thread_count, vars, ...)``
   camera.py   OrbitalCamera (both reference variants)
@@ -14,13 +15,14 @@ the task-mandated name ``mri-raytracer_amd``.  Layout:
   tiles.py    image-tile sharding + RCCL framebuffer gather (one process per GPU)
   synth.py    deterministic synthetic scenes for tests and bench
 """
-from . import _lib, camera, grad, inr, mesh, nifti, params, render, shim, synth, tiles, torch_ops, viewer, volume  # noqa: F401
+from . import _lib, camera, grad, inr, mesh, nifti, params, render, shim, soft, synth, tiles, torch_ops, viewer, volume  # noqa: F401
 from .camera import OrbitalCamera  # noqa: F401
 from .grad import render_brats_autograd, render_brats_backward  # noqa: F401
 from .inr import apply_mlp, build_input, inr_forward, model_load, predict_volume, render_brats_inr  # noqa: F401
 from .mesh import (build_bvh, extract_surface, load_ply, normalize_mesh, render_mesh, surface_mesh,  # noqa: F401
                    upload_mesh)
 from .shim import Device, KernelShim  # noqa: F401
+from .soft import render_brats_soft, render_brats_soft_autograd, render_brats_soft_backward  # noqa: F401
 from .render import (Grid, detile, render_brats, render_sdf, render_volume_u8, tiles_for_rank,  # noqa: F401
                      unbrick_grid, upload_grid, upload_label_cells, upload_mod4)
 

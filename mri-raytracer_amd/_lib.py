@@ -16,7 +16,7 @@ PKG_DIR = pathlib.Path(__file__).resolve().parent
 CSRC = PKG_DIR / "csrc"
 INCLUDE = PKG_DIR.parent / "include"
 SO_PATH = pathlib.Path(os.environ.get("MRIRT_LIB", PKG_DIR / "libmrirt.so"))   # override: A/B builds in development
-HIP_SOURCES = ["brats_march.hip", "brats_skip.hip", "brats_c5.hip", "brats_slab.hip", "brats_ring.hip", "brats_backward.hip", "volume_march.hip", "grid_ops.hip", "inr_mlp.hip",
+HIP_SOURCES = ["brats_march.hip", "brats_skip.hip", "brats_c5.hip", "brats_slab.hip", "brats_ring.hip", "brats_backward.hip", "brats_soft.hip", "volume_march.hip", "grid_ops.hip", "inr_mlp.hip",
                "inr_train.hip", "inr_optim.hip", "inr_muon.hip", "inr_lossx.hip", "mesh_rt.hip", "edt.hip", "surface.hip", "abort_trace.cpp"]
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17", "-Wall"]
 
@@ -31,7 +31,7 @@ ABI_SYMBOLS = [
     "mrirt_sizeof", "mrirt_brats_skip_applicable", "mrirt_brats_kernel_family", "mrirt_install_abort_trace",
     "mrirt_edt_scratch_bytes", "mrirt_edt_squared", "mrirt_hausdorff",
     "mrirt_surface_scratch_bytes", "mrirt_surface_count", "mrirt_surface_extract",
-    "mrirt_render_brats_backward",
+    "mrirt_render_brats_backward", "mrirt_render_brats_soft", "mrirt_render_brats_soft_backward",
     "mrirt_inr_train_scratch_bytes", "mrirt_inr_loss_scratch_bytes", "mrirt_inr_forward_f32", "mrirt_inr_loss", "mrirt_inr_backward",
     "mrirt_inr_sample_batch", "mrirt_inr_adamw_scratch_bytes", "mrirt_inr_adamw_step", "mrirt_inr_lr_schedule",
     "mrirt_inr_train_run_scratch_bytes", "mrirt_inr_train_run",
@@ -376,6 +376,10 @@ def lib() -> C.CDLL:
     l.mrirt_surface_extract.restype = i32
     l.mrirt_render_brats_backward.argtypes = [C.POINTER(BratsParams), C.POINTER(RenderExt), C.POINTER(vp), vp, vp, vp, i64, C.POINTER(vp), vp, vp]
     l.mrirt_render_brats_backward.restype = i32
+    l.mrirt_render_brats_soft.argtypes = [C.POINTER(BratsParams), C.POINTER(RenderExt), C.POINTER(vp), vp, vp, u32, vp, vp, i64, vp, vp]
+    l.mrirt_render_brats_soft.restype = i32
+    l.mrirt_render_brats_soft_backward.argtypes = [C.POINTER(BratsParams), C.POINTER(RenderExt), C.POINTER(vp), vp, vp, u32, vp, vp, i64, vp, vp]
+    l.mrirt_render_brats_soft_backward.restype = i32
     l.mrirt_inr_train_scratch_bytes.argtypes = [C.POINTER(InrDesc), i64]
     l.mrirt_inr_train_scratch_bytes.restype = i64
     l.mrirt_inr_loss_scratch_bytes.argtypes = [i64]

@@ -28,23 +28,6 @@ __device__ __forceinline__ double wave_sum(double v) {
     return v;
 }
 
-// the weighted intensity of one sample as the generic march forms it (brats_march_kernel): ascending modality order
-__device__ __forceinline__ float blend_modalities(const K1Args& a, const Cell& s) {
-    using Mm = M<true>;
-    float v = 0.0f;
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-        if (a.enabled[m] != 0) {
-            Taps<0, false> taps;
-            float sv;
-            taps.template issue<true>(a.vol[m], a.grid, s);
-            taps.template eval<true>(s, sv, nullptr);
-            v = Mm::mad(sv, a.weight[m], v);
-        }
-    }
-    return v;
-}
-
 __global__ __launch_bounds__(256) void brats_backward_kernel(const K1Args a, const BackwardArgs b) {
     __shared__ float4 lutShared[16];
     const float4* lutS = stage_lut(a, lutShared);

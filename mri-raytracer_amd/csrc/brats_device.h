@@ -359,6 +359,24 @@ template <> struct Taps<0, false> {
 };
 template <bool SHADE> struct Taps<1, SHADE> : TapsScalar<1, SHADE> {};
 
+// the weighted intensity of one sample on LINEAR grids as the generic march forms it (brats_march_kernel): ascending modality
+// order, STRICT (the backward passes: brats_backward.hip, brats_soft.hip)
+__device__ __forceinline__ float blend_modalities(const K1Args& a, const Cell& s) {
+    using Mm = M<true>;
+    float v = 0.0f;
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        if (a.enabled[m] != 0) {
+            Taps<0, false> taps;
+            float sv;
+            taps.template issue<true>(a.vol[m], a.grid, s);
+            taps.template eval<true>(s, sv, nullptr);
+            v = Mm::mad(sv, a.weight[m], v);
+        }
+    }
+    return v;
+}
+
 __device__ __forceinline__ uint32_t sample_label(const uint32_t* __restrict__ buf, const LabelAddr& la,
                                                  const float q[3], const float hi[3]) {
     // sampleLabel, brats_rt.slang:78-83; roundf = half away from zero (Metal round)

@@ -158,6 +158,73 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> render_brats_backward(const T
     return { gv[0], gv[1], gv[2], gv[3], gtf };
 }
 
+// The soft prediction overlay (mrirt_render_brats_soft / _backward): the checks the two operators share.  An empty tensor stands
+// for an absent grid, as in render_brats_backward.
+struct SoftBound {
+    MrirtBratsParams P;
+    MrirtRenderExt E;
+    const float* vp[4];
+    const uint32_t* lab;
+    std::optional<at::Device> dev;
+};
+
+SoftBound bind_soft(const Tensor& params, const Tensor& ext, const Tensor& logits, const Tensor& offsets, const OptTensor& vol0,
+                    const OptTensor& vol1, const OptTensor& vol2, const OptTensor& vol3, const OptTensor& labels) {
+    SoftBound b;
+    b.P = unblob<MrirtBratsParams>(params, "MrirtBratsParams");
+    b.E = unblob<MrirtRenderExt>(ext, "MrirtRenderExt");
+    const auto present = [](const OptTensor& t) { return t.has_value() && t->numel() != 0 ? t : OptTensor(); };
+    const OptTensor vols[4] = { present(vol0), present(vol1), present(vol2), present(vol3) };
+    const OptTensor lab = present(labels);
+    const char* names[4] = { "gIntensity0", "gIntensity1", "gIntensity2", "gIntensity3" };
+    const int64_t nvox = (int64_t)b.P.dims[0] * b.P.dims[1] * b.P.dims[2];
+    dev_ptr(logits, at::kFloat, "logits");
+    dev_ptr(offsets, at::kLong, "offsets");
+    same_device(b.dev, logits, "logits");
+    same_device(b.dev, offsets, "offsets");
+    TORCH_CHECK_VALUE(logits.dim() == 2 && logits.size(1) >= 1 && logits.size(1) <= 16, "logits: expected (rows, 1..16 classes)");
+    TORCH_CHECK_VALUE(offsets.numel() == (int64_t)b.P.imageSize[0] * b.P.imageSize[1], "offsets: expected one element per pixel");
+    for (int m = 0; m < 4; ++m) {
+        b.vp[m] = static_cast<const float*>(dev_ptr(vols[m], at::kFloat, names[m]));
+        same_device(b.dev, vols[m], names[m]);
+        TORCH_CHECK_VALUE(b.P.volEnabled[m] == 0 || (vols[m].has_value() && vols[m]->numel() >= nvox),
+                          names[m], " is enabled but holds fewer than ", nvox, " elements");
+    }
+    b.lab = static_cast<const uint32_t*>(dev_ptr(lab, at::kInt, "gLabels"));
+    TORCH_CHECK_VALUE(b.P.showSeg == 0 || (lab.has_value() && lab->numel() >= nvox), "showSeg is set but gLabels is missing or too small");
+    same_device(b.dev, lab, "gLabels");
+    return b;
+}
+
+Tensor render_brats_soft(const Tensor& params, const Tensor& ext, const Tensor& logits, const Tensor& offsets, const OptTensor& vol0,
+                         const OptTensor& vol1, const OptTensor& vol2, const OptTensor& vol3, const OptTensor& labels) {
+    const SoftBound b = bind_soft(params, ext, logits, offsets, vol0, vol1, vol2, vol3, labels);
+    DeviceGuard guard(*b.dev);
+    const int64_t W = b.P.imageSize[0], H = b.P.imageSize[1];
+    Tensor out = at::empty({ H, W, 4 }, at::TensorOptions().dtype(at::kFloat).device(*b.dev));
+    check(mrirt_render_brats_soft(&b.P, &b.E, b.vp, b.lab, logits.data_ptr<float>(), (uint32_t)logits.size(1), offsets.data_ptr<int64_t>(),
+                                  out.data_ptr<float>(), W, nullptr, current_stream()),
+          "mrirt_render_brats_soft");
+    return out;
+}
+
+Tensor render_brats_soft_backward(const Tensor& params, const Tensor& ext, const Tensor& grad_out, const Tensor& logits,
+                                  const Tensor& offsets, const OptTensor& vol0, const OptTensor& vol1, const OptTensor& vol2,
+                                  const OptTensor& vol3, const OptTensor& labels) {
+    SoftBound b = bind_soft(params, ext, logits, offsets, vol0, vol1, vol2, vol3, labels);
+    const int64_t W = b.P.imageSize[0], H = b.P.imageSize[1];
+    const float* g = static_cast<const float*>(dev_ptr(grad_out, at::kFloat, "grad_out"));
+    same_device(b.dev, grad_out, "grad_out");
+    TORCH_CHECK_VALUE(grad_out.dim() == 3 && grad_out.size(0) == H && grad_out.size(1) == W && grad_out.size(2) == 4,
+                      "grad_out: expected (", H, ", ", W, ", 4)");
+    DeviceGuard guard(*b.dev);
+    Tensor dl = at::zeros_like(logits);
+    check(mrirt_render_brats_soft_backward(&b.P, &b.E, b.vp, b.lab, logits.data_ptr<float>(), (uint32_t)logits.size(1),
+                                           offsets.data_ptr<int64_t>(), g, W, dl.data_ptr<float>(), current_stream()),
+          "mrirt_render_brats_soft_backward");
+    return dl;
+}
+
 // volume_cs (scripts/volumeRendering/volume_render.slang:104-148) through mrirt_render_volume
 Tensor render_volume(const Tensor& params, const Tensor& ext, const Tensor& volume, int64_t mode) {
     const MrirtVolumeParams P = unblob<MrirtVolumeParams>(params, "MrirtVolumeParams");
@@ -554,6 +621,10 @@ TORCH_LIBRARY(mrirt_native, m) {
     m.def("render_brats(Tensor params, Tensor ext, Tensor? vol0, Tensor? vol1, Tensor? vol2, Tensor? vol3, Tensor? labels, Tensor? preds) -> Tensor");
     m.def("render_brats_backward(Tensor params, Tensor ext, Tensor grad_out, Tensor? vol0, Tensor? vol1, Tensor? vol2, Tensor? vol3, "
           "Tensor? labels, Tensor? preds) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
+    m.def("render_brats_soft(Tensor params, Tensor ext, Tensor logits, Tensor offsets, Tensor? vol0, Tensor? vol1, Tensor? vol2, Tensor? vol3, "
+          "Tensor? labels) -> Tensor");
+    m.def("render_brats_soft_backward(Tensor params, Tensor ext, Tensor grad_out, Tensor logits, Tensor offsets, Tensor? vol0, Tensor? vol1, "
+          "Tensor? vol2, Tensor? vol3, Tensor? labels) -> Tensor");
     m.def("render_volume(Tensor params, Tensor ext, Tensor volume, int mode) -> Tensor");
     m.def("render_sdf(Tensor params, int width, int height, Tensor like) -> Tensor");
     m.def("render_mesh(Tensor params, Tensor ext, Tensor nodes, Tensor tris, Tensor verts, int max_depth) -> Tensor");
@@ -584,6 +655,8 @@ TORCH_LIBRARY(mrirt_native, m) {
 TORCH_LIBRARY_IMPL(mrirt_native, CompositeExplicitAutograd, m) {
     m.impl("render_brats", &render_brats);
     m.impl("render_brats_backward", &render_brats_backward);
+    m.impl("render_brats_soft", &render_brats_soft);
+    m.impl("render_brats_soft_backward", &render_brats_soft_backward);
     m.impl("render_volume", &render_volume);
     m.impl("render_sdf", &render_sdf);
     m.impl("render_mesh", &render_mesh);

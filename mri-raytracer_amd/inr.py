@@ -13,6 +13,7 @@ model_load, predict_volume``: inr/interactive.ipynb cell 5, inr/viewer/brats_vie
   train_inr(config, cases_or_cache, ...) -> (params, state)             train.py:18-259     (csrc/inr_optim.hip)
   VoxelCache(cases).sample(seed, batch_index, n) / .sample_voxels(...)  dataloader.py:86-96,133-155
   siren_init / make_siren_loss_and_grad / siren_autograd / train_siren   neumors_inr.ipynb:1150-1200 (csrc/inr_train.hip)
+  render_brats_inr_autograd / fit_views                                 docs/Goals.md "gradients flow: pixels -> raytracer -> MLP weights" (csrc/brats_soft.hip)
 
 ``params`` is the reference's list of ``{"W": [in,out], "b": [out]}`` (SIREN: dict ``l{i}`` ->
 ``{"w","b"}``).  All arithmetic runs in csrc/inr_mlp.hip (bf16 MFMA, fp32 accumulate, split-bf16
@@ -1239,3 +1240,86 @@ def train_siren(config: Dict[str, Any], cases_or_cache, val_cases=None, params=N
     out = _siren_dict(st.params())
     state = {"params": out, "w0": w0, **state}
     return out, state
+
+
+# --- differentiable INR render: frame gradients to the MLP weights (csrc/brats_soft.hip) ------------------
+def render_brats_inr_autograd(params, vols, Ws, bs, zmu, zsigma, fourier_freqs: Optional[int] = None, w0: Optional[float] = None,
+                              labels=None, ext=None) -> torch.Tensor:
+    """The per-sample INR render as a differentiable frame, fp32 (H, W, 4), with a ``torch.autograd`` graph to ``Ws`` / ``bs``:
+    counts -> offsets -> ``mrirt_brats_emit_samples`` -> the fp32 training forward (``mlp_autograd`` for a Fourier/ReLU network
+    with ``fourier_freqs``, ``siren_autograd`` for a SIREN with ``w0``; exactly one of the two is given) -> the soft prediction
+    overlay (``render_brats_soft_autograd``).  Where ``render_brats_inr`` draws the argmax class through the LUT, this frame
+    draws the class probabilities, so ``frame.backward()`` reaches every weight.
+
+    ``params``: the gParams dict; ``vols``: the four LINEAR fp32 device tensors of X*Y*Z voxels the MLP reads; ``Ws`` / ``bs``:
+    the layers' (in, out) / (out,) device tensors; ``zmu`` / ``zsigma``: the viewer's per-modality z-score constants.  The
+    sample total is read to the host once per call (as ``render_brats_inr(one_pass=True)``); the activations of every march
+    sample of the frame stay on the device until the backward pass."""
+    from .render import _bind_brats
+    from .soft import render_brats_soft_autograd
+    if (fourier_freqs is None) == (w0 is None):
+        raise ValueError("give fourier_freqs (Fourier/ReLU network) or w0 (SIREN), not both")
+    dev = _require_gpu()
+    P, E, v, _, _, _ = _bind_brats(params, list(vols), labels, None, ext, dev, pred_stream=True)
+    if len(v) != 4 or any(t is None for t in v):
+        raise ValueError("the MLP reads all four modalities: bind four volumes")
+    if E.layout != _lib.LAYOUT_LINEAR or E.tileSize > 0:
+        raise ValueError("render_brats_inr_autograd: whole frames on LINEAR grids only")
+    w, h = int(P.imageSize[0]), int(P.imageSize[1])
+    lib, s = _lib.lib(), _stream_ptr(None)
+    vp = (C.c_void_p * 4)(*[C.c_void_p(t.data_ptr()) for t in v])
+    mu = (C.c_float * 4)(*[float(np.float32(x)) for x in zmu])
+    sg = (C.c_float * 4)(*[float(np.float32(x)) for x in zsigma])
+    counts = torch.empty(h * w, dtype=torch.int32, device=dev)
+    _lib.check(lib.mrirt_brats_sample_counts(C.byref(P), C.byref(E), _ptr(counts), s), "mrirt_brats_sample_counts")
+    ends = torch.cumsum(counts.to(torch.int64), 0)
+    offsets = (ends - counts).contiguous()
+    total = int(ends[-1])                                       # the one host read of the call
+    n = max(total, 1)
+    coords = torch.zeros((n, 3), dtype=torch.float32, device=dev)
+    feats = torch.zeros((n, 4), dtype=torch.float32, device=dev)
+    _lib.check(lib.mrirt_brats_emit_samples(C.byref(P), C.byref(E), vp, mu, sg, _ptr(offsets), _ptr(coords), _ptr(feats), s),
+               "mrirt_brats_emit_samples")
+    Ws, bs = list(Ws), list(bs)
+    logits = siren_autograd(Ws, bs, coords, feats, float(w0)) if w0 is not None else mlp_autograd(Ws, bs, coords, feats, int(fourier_freqs))
+    return render_brats_soft_autograd(params, v, logits, offsets, labels, ext)
+
+
+def fit_views(config: Dict[str, Any], views: Sequence[Dict[str, Any]], targets: Sequence[torch.Tensor], vols, params, gparams, zmu, zsigma,
+              labels=None, ext=None, log=None) -> Tuple[List[float], AdamWState]:
+    """Fit a network to target frames: per step the mean over the pixels and the three colour channels of
+    (frame - target)^2, summed over the views, through ``render_brats_inr_autograd``; one clipped AdamW update per step
+    (``adamw_step``) at the rate of ``lr_schedule``.  The reference's "differentiability proof" (docs/Goals.md).
+
+    ``views``: per view the gParams entries it overrides (``eye``, ``U``, ``V``, ``W``, ...); ``targets``: per view a device fp32
+    (H, W, 4) frame; ``params``: the start, a list of ``{"W", "b"}`` (Fourier/ReLU) or the SIREN dict ``l{i} -> {"w", "b"}``.
+    ``config``: ``STEPS``, ``LR`` (peak), ``MIN_LR`` (default ``LR``), ``WARMUP_STEPS`` (0), ``DECAY_STEPS`` (``STEPS`` + 1),
+    ``CLIP_NORM`` (0: none), ``WEIGHT_DECAY`` (0), and ``FOURIER_FREQS`` or ``W0`` as the network's kind demands.
+    Returns ``(losses, state)``: the loss of every step before its update (host floats) and the ``AdamWState``."""
+    if len(views) != len(targets) or not views:
+        raise ValueError("one target frame per view, at least one view")
+    siren = isinstance(params, dict)
+    layers = [{"W": params[f"l{i}"]["w"], "b": params[f"l{i}"]["b"]} for i in range(len(params))] if siren else list(params)
+    if siren == ("FOURIER_FREQS" in config and int(config["FOURIER_FREQS"]) != 0):
+        raise ValueError("a SIREN dict takes W0, a list of layers takes FOURIER_FREQS")
+    kind = dict(w0=float(config.get("W0", 30.0))) if siren else dict(fourier_freqs=int(config["FOURIER_FREQS"]))
+    steps, peak = int(config["STEPS"]), float(config["LR"])
+    end, warmup = float(config.get("MIN_LR", peak)), int(config.get("WARMUP_STEPS", 0))
+    decay, clip, wd = int(config.get("DECAY_STEPS", steps + 1)), float(config.get("CLIP_NORM", 0.0)), float(config.get("WEIGHT_DECAY", 0.0))
+    st = AdamWState.from_params(layers)
+    losses = []
+    for step in range(steps):
+        leaves = [{k: t.detach().requires_grad_(True) for k, t in g.items()} for g in _split_grads(st.w, st.b, st.dims)]
+        Ws, bs = [g["W"] for g in leaves], [g["b"] for g in leaves]
+        loss = None
+        for view, target in zip(views, targets):
+            frame = render_brats_inr_autograd({**gparams, **view}, vols, Ws, bs, zmu, zsigma, labels=labels, ext=ext, **kind)
+            term = ((frame[..., :3] - target[..., :3]) ** 2).mean()
+            loss = term if loss is None else loss + term
+        loss.backward()
+        gw, gb = (torch.cat([(t.grad if t.grad is not None else torch.zeros_like(t)).reshape(-1) for t in ts]) for ts in (Ws, bs))
+        adamw_step(st, gw, gb, lr_schedule(peak, end, warmup, decay, st.step), clip_norm=clip, weight_decay=wd)
+        losses.append(float(loss.detach()))
+        if log is not None:
+            log(step, losses[-1])
+    return losses, st

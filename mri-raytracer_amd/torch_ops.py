@@ -223,6 +223,78 @@ def _(params, ext, grad_out, vol0, vol1, vol2, vol3, labels, preds):
     return gv[0], gv[1], gv[2], gv[3], torch.empty(4, dtype=torch.float64, device=grad_out.device)
 
 
+# --- K1 soft prediction overlay -------------------------------------------------------------------
+def _bind_soft(params, ext, logits, offsets, vols, labels, frame_like=None):
+    """The checks the two soft-overlay operators share; returns (P, E, vol pointers, labels, device)."""
+    P, E = _unblob(params, _lib.BratsParams), _unblob(ext, _lib.RenderExt)
+    dims = [int(v) for v in P.dims]
+    nvox = dims[0] * dims[1] * dims[2]
+    W, H = int(P.imageSize[0]), int(P.imageSize[1])
+    vols = [_dev_flat(_present(v), torch.float32, f"gIntensity{m}") for m, v in enumerate(vols)]
+    lab = _dev_flat(_present(labels), torch.int32, "gLabels")
+    z = _dev_flat(logits, torch.float32, "logits")
+    off = _dev_flat(offsets, torch.int64, "offsets")
+    if z.dim() != 2 or not 1 <= int(z.shape[1]) <= 16:
+        raise ValueError(f"logits: expected (rows, 1..16 classes), got {tuple(z.shape)}")
+    if off.numel() != W * H:
+        raise ValueError(f"offsets: expected {W * H} elements (one per pixel), got {off.numel()}")
+    for m, v in enumerate(vols):
+        if P.volEnabled[m] != 0 and (v is None or v.numel() < nvox):
+            raise ValueError(f"gIntensity{m} is enabled but holds {0 if v is None else v.numel()} < {nvox} elements")
+    if P.showSeg != 0 and (lab is None or lab.numel() < nvox):
+        raise ValueError("showSeg is set but gLabels is missing or too small")
+    if frame_like is not None and tuple(frame_like.shape) != (H, W, 4):
+        raise ValueError(f"grad_out: expected ({H}, {W}, 4), got {tuple(frame_like.shape)}")
+    dev = _one_device([("logits", z), ("offsets", off), ("grad_out", frame_like)] + [(f"gIntensity{m}", v) for m, v in enumerate(vols)]
+                      + [("gLabels", lab)])
+    vp = (C.c_void_p * 4)(*[C.c_void_p(v.data_ptr()) if v is not None else None for v in vols])
+    return P, E, vp, lab, dev
+
+
+@torch.library.custom_op("mrirt::render_brats_soft", mutates_args=())
+def render_brats_soft(params: torch.Tensor, ext: torch.Tensor, logits: torch.Tensor, offsets: torch.Tensor,
+                      vol0: Optional[torch.Tensor], vol1: Optional[torch.Tensor], vol2: Optional[torch.Tensor],
+                      vol3: Optional[torch.Tensor], labels: Optional[torch.Tensor]) -> torch.Tensor:
+    """The soft-overlay K1 frame through mrirt_render_brats_soft: ``logits`` fp32 [rows, C], ``offsets`` int64 [H * W] (row of
+    the first sample of every pixel); LINEAR fp32 grids.  Returns fp32 [H, W, 4]."""
+    P, E, vp, lab, dev = _bind_soft(params, ext, logits, offsets, (vol0, vol1, vol2, vol3), labels)
+    W, H = int(P.imageSize[0]), int(P.imageSize[1])
+    with torch.cuda.device(dev):
+        out = torch.empty((H, W, 4), dtype=torch.float32, device=dev)
+        rc = _lib.lib().mrirt_render_brats_soft(C.byref(P), C.byref(E), vp, _ptr(lab), _ptr(logits), int(logits.shape[1]), _ptr(offsets),
+                                                _ptr(out), W, None, _stream())
+    _lib.check(rc, "mrirt_render_brats_soft")
+    return out
+
+
+@render_brats_soft.register_fake
+def _(params, ext, logits, offsets, vol0, vol1, vol2, vol3, labels):
+    P = _unblob(params, _lib.BratsParams)
+    return torch.empty((int(P.imageSize[1]), int(P.imageSize[0]), 4), dtype=torch.float32, device=logits.device)
+
+
+@torch.library.custom_op("mrirt::render_brats_soft_backward", mutates_args=())
+def render_brats_soft_backward(params: torch.Tensor, ext: torch.Tensor, grad_out: torch.Tensor, logits: torch.Tensor,
+                               offsets: torch.Tensor, vol0: Optional[torch.Tensor], vol1: Optional[torch.Tensor],
+                               vol2: Optional[torch.Tensor], vol3: Optional[torch.Tensor], labels: Optional[torch.Tensor]
+                               ) -> torch.Tensor:
+    """dL/dlogits of the soft-overlay frame through mrirt_render_brats_soft_backward: ``grad_out`` is dL/dframe, fp32
+    [H, W, 4] (alpha ignored).  Returns fp32 shaped like ``logits``, allocated zeroed (rows no ray owns stay zero)."""
+    g = _dev_flat(grad_out, torch.float32, "grad_out")
+    P, E, vp, lab, dev = _bind_soft(params, ext, logits, offsets, (vol0, vol1, vol2, vol3), labels, frame_like=g)
+    with torch.cuda.device(dev):
+        dl = torch.zeros_like(logits)
+        rc = _lib.lib().mrirt_render_brats_soft_backward(C.byref(P), C.byref(E), vp, _ptr(lab), _ptr(logits), int(logits.shape[1]),
+                                                         _ptr(offsets), _ptr(g), int(P.imageSize[0]), _ptr(dl), _stream())
+    _lib.check(rc, "mrirt_render_brats_soft_backward")
+    return dl
+
+
+@render_brats_soft_backward.register_fake
+def _(params, ext, grad_out, logits, offsets, vol0, vol1, vol2, vol3, labels):
+    return torch.empty_like(logits)
+
+
 # --- K2 -----------------------------------------------------------------------------------------
 _VOX_DTYPE = {_lib.VOX_U32X4: torch.int32, _lib.VOX_U8: torch.uint8, _lib.VOX_F32: torch.float32}
 
