@@ -1,4 +1,4 @@
-// C5: the per-sample INR render of K1's rays — every sample point of the march is classified by the tiny MLP (inr_mlp.hip)
+// C5: the per-sample INR render of K1's rays — every sample point of the march is classified by the tiny MLP (inr_mlp.hip and its kernel units)
 // and composited with the class as the prediction overlay.  Build-defined extension.  Two forms:
 //   whole-ray: mrirt_brats_sample_counts + mrirt_brats_emit_samples write every sample's MLP inputs, the caller classifies
 //              them, and mrirt_render_brats_stream (brats_march.hip: the generic kernel) marches with the class stream;
@@ -100,7 +100,7 @@ __global__ __launch_bounds__(256) void emit_samples_kernel(const K1Args a, const
 //              memory (no host round trip);
 //   emit:      one thread per row of the batch writes that sample's MLP inputs and what the compositor needs of it
 //              besides the class (weighted intensity, gradient when shading, seg label);
-//   classify:  mrirt's MFMA forward over that batch (inr_mlp.hip, point count read from the device word);
+//   classify:  mrirt's MFMA forward over that batch (inr_forward_dev_n of inr_mlp.hip, point count read from the device word);
 //   composite: the same rays composite those steps from the per-row records, exactly as brats_main does (ERT tested
 //              before every step), park their state (t, T, C) — and plan the NEXT pass (the plan kernel itself only
 //              runs for the first one).

@@ -1,6 +1,6 @@
 // The host-side seam between the K1 units: what brats_march.hip (the march, its plan and prepare()), brats_skip.hip (the
 // skipping pre-pass), brats_c5.hip (the per-sample INR render), brats_slab.hip / brats_ring.hip (the LDS marches) and
-// inr_mlp.hip call across translation units.  tests/native/index_harness.hip reaches prepare() through this header.
+// inr_mlp.hip (the INR forward's host side; its kernels: inr_fwd.h) call across translation units.  tests/native/index_harness.hip reaches prepare() through this header.
 #pragma once
 #include "brats_device.h"
 

@@ -16,7 +16,8 @@ model_load, predict_volume``: inr/interactive.ipynb cell 5, inr/viewer/brats_vie
   render_brats_inr_autograd / fit_views                                 docs/Goals.md "gradients flow: pixels -> raytracer -> MLP weights" (csrc/brats_soft.hip)
 
 ``params`` is the reference's list of ``{"W": [in,out], "b": [out]}`` (SIREN: dict ``l{i}`` ->
-``{"w","b"}``).  All arithmetic runs in csrc/inr_mlp.hip (bf16 MFMA, fp32 accumulate, split-bf16
+``{"w","b"}``).  All arithmetic runs in the kernels behind csrc/inr_mlp.hip
+(inr_stream.hip, inr_ws.hip, inr_refine.hip: bf16 MFMA, fp32 accumulate, split-bf16
 first layer); ``model_load`` is host-side file parsing.  No CPU fallback.
 """
 from __future__ import annotations

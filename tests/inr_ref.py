@@ -1,4 +1,5 @@
-"""Plain NumPy references for the INR forward (csrc/inr_mlp.hip), and the networks of the shape sweep.  No GPU, no torch.
+"""Plain NumPy references for the INR forward (csrc/inr_mlp.hip and its kernel units inr_stream.hip, inr_ws.hip, inr_refine.hip),
+the networks of the shape sweep, and the packed weight image.  No GPU, no torch.
 
   forward64      the network in fp64: what the kernels approximate
   emulate_bf16   the error model of the bf16 pass: every operand rounded where the kernel rounds it (layer-0 inputs, weights
@@ -11,7 +12,10 @@
                  integer somewhere, because every row of every matrix is used.
 
 The sweep's nets (EXACT_NETS, FOURIER0_NETS, SINE_NETS) are listed here so that the host test can check their preconditions on
-the CPU for exactly the seeds the GPU test uses."""
+the CPU for exactly the seeds the GPU test uses.
+
+  pack_image     the packed weight image of mrirt_inr_pack_weights (main and refine), written from the layout comments;
+                 PACK_NETS / pack_case are the networks tests/test_gpu_inr_pack.py packs."""
 import numpy as np
 
 KIND_FOURIER_RELU, KIND_SIREN, KIND_RAW_RELU, KIND_RAW_SIREN = 0, 1, 2, 3
@@ -269,3 +273,106 @@ def sine_case(i):
         return layers, None, x, x.astype(np.float64)
     feats = rng.standard_normal((N_POINTS, net["M"])).astype(np.float32) if net["M"] else None
     return layers, coords, feats, build_input64(coords, feats, net["K"])
+
+
+# ---- the packed image ------------------------------------------------------------------------------------------------------------
+# Written from the layout comments of csrc/inr_mlp.hip / csrc/inr_fwd.h, not from the pack kernel: a 1-KiB fragment is one
+# (out tile o, k tile t, k step s) of a layer as 64 lanes x 8 bf16; lane 32 h + r holds output column 32 o + r, and its element j
+# input row  32 t + 16 s + 8 (j >> 2) + 4 h + (j & 3).  The layer's scale is folded into the fp32 weight before rounding;
+# hi = bf16(v), lo = bf16(v - hi); rows and columns beyond the layer's true widths are zero.
+#   main image:    layer 0 of a split SIREN [o][t][s][hi, lo], every other layer [o][t][s] (hi only)
+#   refine image:  every layer [o][t][s][hi, lo]
+#   both:          layer 0 of a KIND_SIREN net with <= 8 inputs ("augmented") is ONE k tile whose 32 rows are
+#                  k step 0 = [W_hi ; W_hi ; 0] (16 rows), k step 1 = [W_lo ; 0] (16 rows): [o][s]
+PACK_SLACK_FRAGS, REF_SLACK_FRAGS = 64, 32          # after the main image / after the refine image; then one calibration fragment
+
+
+def _bf16_bits(a64):
+    """uint16 patterns of values that are exactly representable in bf16."""
+    f = np.asarray(a64, np.float64).astype(np.float32)
+    assert np.array_equal(f.astype(np.float64), a64)
+    return (f.view(np.uint32) >> 16).astype(np.uint16)
+
+
+def _fragments(rows_bits, kt, ot):
+    """(32 kt, 32 ot) uint16 -> (ot, kt, 2, 64, 8): fragment [o][t][s], lane, element."""
+    j, h = np.arange(8), np.arange(2)
+    k_in_step = 8 * (j[None, :] >> 2) + 4 * h[:, None] + (j[None, :] & 3)                   # [h][j]
+    out = np.zeros((ot, kt, 2, 64, 8), np.uint16)
+    for o in range(ot):
+        for t in range(kt):
+            for s in range(2):
+                blk = rows_bits[32 * t + 16 * s + k_in_step][:, :, 32 * o:32 * o + 32]        # [h][j][r]
+                out[o, t, s] = blk.transpose(0, 2, 1).reshape(64, 8)
+    return out
+
+
+def pack_image(layers, kind, w0=30.0, refine=False):
+    """The main (refine=False) or the refine image of the network as (fragments, 64, 8) uint16."""
+    wb = _wb(layers)
+    siren = _is_siren(kind)
+    in_dim, hidden = wb[0][0].shape
+    aug = kind == KIND_SIREN and in_dim <= 8
+    frags = []
+    for i, (W, _) in enumerate(wb):
+        head = i + 1 == len(wb)
+        fold = siren and not head
+        scale = np.float32(((float(w0) if i == 0 else 1.0) / TWO_PI_F32) if fold else 1.0)
+        v = (W.astype(np.float32) * scale).astype(np.float64)                                 # the fp32 product that is rounded
+        hi = bf16_round(v)
+        lo = bf16_round(v - hi)
+        kt = (1 if in_dim <= 32 else 4) if i == 0 else hidden // 32
+        ot = (W.shape[1] + 31) // 32
+
+        def padded(m):
+            p = np.zeros((32 * kt, 32 * ot), np.uint16)
+            p[:m.shape[0], :m.shape[1]] = _bf16_bits(m)
+            return p
+        if i == 0 and aug:
+            z = np.zeros((16 - 2 * in_dim, W.shape[1]))
+            folded = np.concatenate([hi, hi, z, lo, np.zeros((16 - in_dim, W.shape[1]))], 0)     # 32 rows
+            frags.append(_fragments(padded(folded), 1, ot).reshape(-1, 64, 8))
+        elif refine or (i == 0 and siren):
+            both = np.stack([_fragments(padded(hi), kt, ot), _fragments(padded(lo), kt, ot)], 3)  # [o][t][s][hi, lo]
+            frags.append(both.reshape(-1, 64, 8))
+        else:
+            frags.append(_fragments(padded(hi), kt, ot).reshape(-1, 64, 8))
+    return np.concatenate(frags, 0)
+
+
+# The smallest networks that reach every branch of the pack kernel: kind, K, M, in, hidden, layers, out, w0
+PACK_NETS = [
+    dict(kind=KIND_FOURIER_RELU, K=1, M=1, ind=10, hidden=32, layers=2, out=1, w0=0.0),      # one k tile, no split
+    dict(kind=KIND_FOURIER_RELU, K=5, M=0, ind=33, hidden=32, layers=3, out=16, w0=0.0),     # kt0 = 4, zero padding to 128, padded head columns
+    dict(kind=KIND_SIREN, K=0, M=4, ind=7, hidden=32, layers=3, out=4, w0=30.0),             # augmented split
+    dict(kind=KIND_SIREN, K=0, M=5, ind=8, hidden=32, layers=3, out=4, w0=1.0),              # augmented split with k step 0 full
+    dict(kind=KIND_SIREN, K=0, M=6, ind=9, hidden=64, layers=3, out=4, w0=30.0),             # hi/lo split of layer 0, scale on hidden layers
+    dict(kind=KIND_RAW_RELU, K=0, M=0, ind=1, hidden=32, layers=2, out=2, w0=0.0),           # raw ReLU
+    dict(kind=KIND_RAW_SIREN, K=0, M=0, ind=33, hidden=64, layers=3, out=3, w0=30.0),        # raw sine, split with kt0 = 4
+]
+PACK_SEED = 3000                    # net i uses seed PACK_SEED + i
+# Exactly half-way between two bf16 numbers (round-to-nearest-even: down to 1, up to 1 + 2^-6, down in magnitude to -0.5, up
+# to 2^-20 (1 + 2^-6)), and one whose lo part is itself a tie (1 + 2^-10 + 2^-18: hi = 1, lo -> 2^-10).  Planted in the layers
+# whose folded scale is 1, where the fp32 product is the value itself.
+PACK_TIES = np.array([1.0 + 2.0 ** -8, 1.0 + 3 * 2.0 ** -8, -(0.5 + 2.0 ** -9), 2.0 ** -20 * (1.0 + 3 * 2.0 ** -8),
+                      1.0 + 2.0 ** -10 + 2.0 ** -18], np.float32)
+
+
+def pack_id(net):
+    return "kind%d_in%d_h%d_L%d_o%d" % (net["kind"], net["ind"], net["hidden"], net["layers"], net["out"])
+
+
+def pack_case(i):
+    """Net i of PACK_NETS: layers [{"W", "b"}] of seeded normals with PACK_TIES planted in every layer of scale 1."""
+    net = PACK_NETS[i]
+    rng = np.random.default_rng(PACK_SEED + i)
+    dims = [net["ind"]] + [net["hidden"]] * (net["layers"] - 1) + [net["out"]]
+    layers = []
+    for l in range(len(dims) - 1):
+        W = rng.standard_normal((dims[l], dims[l + 1])).astype(np.float32)
+        if not _is_siren(net["kind"]) or l + 2 == len(dims):
+            flat = W.reshape(-1)
+            n = min(len(PACK_TIES), flat.size)
+            flat[rng.choice(flat.size, n, replace=False)] = PACK_TIES[:n]
+        layers.append({"W": W, "b": np.zeros(dims[l + 1], np.float32)})
+    return layers

@@ -26,7 +26,8 @@ def build_harness() -> pathlib.Path:
     OUT.mkdir(parents=True, exist_ok=True)
     exe = OUT / "index_harness"
     srcs = [ROOT / "tests" / "native" / "index_harness.hip"] + [
-        CSRC / s for s in ("brats_march.hip", "brats_skip.hip", "brats_c5.hip", "brats_slab.hip", "brats_ring.hip", "grid_ops.hip", "inr_mlp.hip")]
+        CSRC / s for s in ("brats_march.hip", "brats_skip.hip", "brats_c5.hip", "brats_slab.hip", "brats_ring.hip", "grid_ops.hip", "inr_mlp.hip", "inr_stream.hip",
+                             "inr_ws.hip", "inr_refine.hip")]
     deps = srcs + list(CSRC.glob("*.h")) + [ROOT / "include" / "mrirt.h"]
     if exe.exists() and exe.stat().st_mtime >= max(p.stat().st_mtime for p in deps):
         return exe

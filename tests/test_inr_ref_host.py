@@ -170,3 +170,38 @@ def test_sine_nets_exclude_at_most_one_per_cent(i):
     assert excluded <= 0.01, excluded
     err = np.abs(ir.emulate_bf16(layers, x, net["kind"], net["w0"]) - ref).max()
     assert 0 < err < np.inf
+
+
+@pytest.mark.parametrize("i", range(len(ir.PACK_NETS)), ids=[ir.pack_id(n) for n in ir.PACK_NETS])
+def test_numpy_packer_decodes_to_the_scaled_weights(i):
+    """pack_image, read back element by element with the index formula of the layout comment: hi + lo of the refine image is
+    the scaled fp32 weight to 2^-16, padding is zero, the main image is the refine image's hi parts (layer 0 of a split SIREN:
+    both parts), and the fragment count is make_layout's."""
+    net, layers = ir.PACK_NETS[i], ir.pack_case(i)
+    siren = net["kind"] in (ir.KIND_SIREN, ir.KIND_RAW_SIREN)
+    aug = net["kind"] == ir.KIND_SIREN and net["ind"] <= 8
+    main, ref = ir.pack_image(layers, net["kind"], net["w0"]), ir.pack_image(layers, net["kind"], net["w0"], refine=True)
+    assert len(main) == ir.total_frags(net["ind"], net["hidden"], net["layers"], net["out"], siren and not aug)
+    val = lambda bits: (bits.astype(np.uint32) << 16).view(np.float32).astype(np.float64)
+    fm = fr = 0
+    for l, p in enumerate(layers):
+        head = l + 1 == len(layers)
+        scale = np.float32(((net["w0"] if l == 0 else 1.0) / ir.TWO_PI_F32) if siren and not head else 1.0)
+        v = (p["W"] * scale).astype(np.float64)
+        kt, ot = ((1 if net["ind"] <= 32 else 4) if l == 0 else net["hidden"] // 32), (p["W"].shape[1] + 31) // 32
+        n = ot * kt * 2
+        if l == 0 and aug:
+            assert np.array_equal(main[fm:fm + n], ref[fr:fr + n])
+            fm, fr = fm + n, fr + n
+            continue
+        pair = ref[fr:fr + 2 * n].reshape(ot, kt, 2, 2, 64, 8)
+        split_main = l == 0 and siren
+        assert np.array_equal(main[fm:fm + (2 * n if split_main else n)].reshape(-1),
+                              (pair if split_main else pair[:, :, :, 0]).reshape(-1))
+        for o, t, s, lane, j in itertools.product(range(ot), range(kt), range(2), range(0, 64, 7), range(8)):
+            k, c = 32 * t + 16 * s + 8 * (j >> 2) + 4 * (lane >> 5) + (j & 3), 32 * o + (lane & 31)
+            want = v[k, c] if k < v.shape[0] and c < v.shape[1] else 0.0
+            got = val(pair[o, t, s, 0, lane, j]) + val(pair[o, t, s, 1, lane, j])
+            assert abs(got - want) <= 2.0 ** -16 * abs(want), (l, o, t, s, lane, j)
+        fm, fr = fm + (2 * n if split_main else n), fr + 2 * n
+    assert fm == len(main) and fr == len(ref)

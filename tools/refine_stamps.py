@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Decode the s_memtime stamps of a -DMRIRT_REF_STAMPS build of inr_refine_kernel (bash tools/build_variant.sh REFSTAMPS inr_mlp.hip -DMRIRT_REF_STAMPS; MRIRT_LIB=build_exp/libmrirt_REFSTAMPS.so):
+"""Decode the s_memtime stamps of a -DMRIRT_REF_STAMPS build of inr_refine_kernel (bash tools/build_variant.sh REFSTAMPS inr_refine.hip -DMRIRT_REF_STAMPS; MRIRT_LIB=build_exp/libmrirt_REFSTAMPS.so):
 median shader cycles per phase of the second batch of every workgroup, and the clock they imply."""
 import math, os, sys, time
 import numpy as np

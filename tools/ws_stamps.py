@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Decode the s_memtime stamps of a -DMRIRT_WS_STAMPS build (MRIRT_LIB=build_exp/libmrirt_WSSTAMPS.so):
+"""Decode the s_memtime stamps of a -DMRIRT_WS_STAMPS build of inr_ws_kernel (bash tools/build_variant.sh WSSTAMPS inr_ws.hip -DMRIRT_WS_STAMPS;
+MRIRT_LIB=build_exp/libmrirt_WSSTAMPS.so):
 median cycles per phase of one steady-state round, over all workgroups, per wave."""
 import os, sys, math, numpy as np, torch
 sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
