@@ -223,7 +223,8 @@ def test_torch_ops_are_registered_with_shape_functions():
 
 def test_native_operator_library_builds_and_registers():
     """csrc/torch_binding.cpp (the C++ PyTorch extension over the C ABI): compiles against this torch, loads without a
-    GPU, registers the three render operators, and its argument checks fire before anything touches the device."""
+    GPU, registers its operators (all 19: tests/test_torch_ops_contract.py), and its argument checks fire before anything touches
+    the device."""
     import torch
     from mrirt import torch_ops
     _lib.build_torch_binding()
