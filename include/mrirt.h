@@ -358,6 +358,41 @@ typedef enum MrirtKernelFamily {
 int mrirt_brats_kernel_family(const MrirtBratsParams* params, const MrirtRenderExt* ext, const void* const vol[4],
                               const void* labels, const void* preds, const MrirtSkip* skip);
 
+/* Dispatch order (build-defined scheduling; the frame and the counters are the same bits under any order: every ray is
+ * independent).  The march records per workgroup how many steps its longest ray took (`steps`), and before the next frame
+ * a small kernel on the same stream bins each XCD's workgroups into `classes` classes by those steps — thresholds at the
+ * XCD's own quantiles — and writes `order`: the classes longest first, the launch's own order inside a class, every
+ * workgroup on the XCD it had; then it zeroes `steps`.  The long ray packets so start in the first rounds of a launch
+ * and its tail is made of short ones.  A zeroed record gives the identity, so a scratch starts as zeros in `steps`
+ * (`order` needs no initial value); a record from another camera or scene can only cost time.
+ * classes: 1 .. 16, 0 = the caller's own table: no builder runs, `order` is read as it stands (entries that are no
+ * permutation leave pixels unwritten or written twice, never memory outside the frame and the record) and `steps`
+ * accumulates maxima until the caller zeroes it.
+ * One scratch per stream: frames in flight on different streams must not share a record.                              */
+typedef struct MrirtOrder {
+    uint32_t* order;              /* `words` uint32: order[b] = the pixel-map position workgroup b marches           */
+    uint32_t* steps;              /* `words` uint32: the record, by pixel-map position (the index space of `order`'s values) */
+    uint32_t words;               /* >= mrirt_order_words(imageSize, ext) (checked)                                   */
+    uint32_t classes;
+} MrirtOrder;
+/* words of both tables for an untiled launch of this image size (ext: layout and kernelVariant decide the workgroup size);
+ * 0: a tiled launch or an empty image — no ordering */
+int64_t mrirt_order_words(const uint32_t imageSize[2], const MrirtRenderExt* ext);
+/* mrirt_render_brats_skip with a dispatch order.  Ordered launches are the pipelined and rolling kernel families, whole
+ * frame (tileSize == 0), marching without an empty-radius map; any other launch, or order == NULL, ignores the scratch
+ * and is mrirt_render_brats_skip. */
+int mrirt_render_brats_ordered(const MrirtBratsParams* params, const MrirtRenderExt* ext,
+                               const void* const vol[4], const void* labels, const void* preds,
+                               const MrirtSkip* skip, const MrirtOrder* order, void* out_rgba, int64_t pitch_px,
+                               uint64_t* stats_dev, void* stream);
+/* Host-only query, nothing is launched: 1 = mrirt_render_brats_ordered with these arguments and a scratch orders its
+ * launch, 0 = it ignores the scratch; < 0: the MrirtStatus the render call would return. */
+int mrirt_brats_order_applicable(const MrirtBratsParams* params, const MrirtRenderExt* ext, const void* const vol[4],
+                                 const void* labels, const void* preds, const MrirtSkip* skip);
+/* Host-only: the table the builder kernel writes for this record, for `words` workgroups (any count) and `classes` as above
+ * (0 = 4); `steps` is left as it is. */
+int mrirt_order_build_host(const uint32_t* steps, uint32_t words, uint32_t classes, uint32_t* order);
+
 /* ------------------------------------------------------------------------------------ */
 /* number of tiles rank `rank` of `world` renders for a W x H image */
 int64_t mrirt_tiles_for_rank(uint32_t width, uint32_t height, uint32_t tileSize, uint32_t rank, uint32_t world);

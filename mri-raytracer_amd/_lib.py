@@ -16,7 +16,7 @@ PKG_DIR = pathlib.Path(__file__).resolve().parent
 CSRC = PKG_DIR / "csrc"
 INCLUDE = PKG_DIR.parent / "include"
 SO_PATH = pathlib.Path(os.environ.get("MRIRT_LIB", PKG_DIR / "libmrirt.so"))   # override: A/B builds in development
-HIP_SOURCES = ["brats_march.hip", "brats_skip.hip", "brats_c5.hip", "brats_slab.hip", "brats_ring.hip", "brats_backward.hip", "brats_soft.hip", "volume_march.hip", "grid_ops.hip", "inr_mlp.hip",
+HIP_SOURCES = ["brats_march.hip", "brats_order.hip", "brats_skip.hip", "brats_c5.hip", "brats_slab.hip", "brats_ring.hip", "brats_backward.hip", "brats_soft.hip", "volume_march.hip", "grid_ops.hip", "inr_mlp.hip",
                "inr_stream.hip", "inr_ws.hip", "inr_refine.hip", "inr_train.hip", "inr_optim.hip", "inr_muon.hip", "inr_lossx.hip", "mesh_rt.hip", "edt.hip", "surface.hip", "abort_trace.cpp"]
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17", "-Wall"]
 
@@ -41,6 +41,7 @@ ABI_SYMBOLS = [
     "mrirt_inr_train_run_muon_scratch_bytes", "mrirt_inr_train_run_muon",
     "mrirt_inr_loss_ext_scratch_bytes", "mrirt_inr_loss_ext", "mrirt_inr_tumour_count", "mrirt_inr_tumour_index_scratch_bytes",
     "mrirt_inr_tumour_index", "mrirt_inr_sample_batch_mix", "mrirt_inr_train_run_ext_scratch_bytes", "mrirt_inr_train_run_ext",
+    "mrirt_order_words", "mrirt_render_brats_ordered", "mrirt_brats_order_applicable", "mrirt_order_build_host",
 ]
 
 ABI_VERSION = 4          # MRIRT_ABI_VERSION of include/mrirt.h this binding was written against
@@ -170,6 +171,11 @@ class Skip(C.Structure):
     """MrirtSkip: macro-cell summaries + mask scratch for exact empty-space skipping."""
     _fields_ = [("macroUb", C.c_void_p * 4), ("macroSeg", C.c_void_p), ("macroPred", C.c_void_p), ("mask", C.c_void_p),
                 ("maskWords", u32), ("mapReady", u32)]
+
+
+class Order(C.Structure):
+    """MrirtOrder: the dispatch-order table and the step record of one stream's K1 launches."""
+    _fields_ = [("order", C.c_void_p), ("steps", C.c_void_p), ("words", u32), ("classes", u32)]
 
 
 class MrirtError(RuntimeError):
@@ -342,6 +348,15 @@ def lib() -> C.CDLL:
     l.mrirt_brats_skip_applicable.restype = i32
     l.mrirt_brats_kernel_family.argtypes = l.mrirt_brats_skip_applicable.argtypes
     l.mrirt_brats_kernel_family.restype = i32
+    l.mrirt_order_words.argtypes = [C.POINTER(u32), C.POINTER(RenderExt)]
+    l.mrirt_order_words.restype = i64
+    l.mrirt_render_brats_ordered.argtypes = [C.POINTER(BratsParams), C.POINTER(RenderExt), C.POINTER(vp), vp, vp, C.POINTER(Skip), C.POINTER(Order),
+                                             vp, i64, vp, vp]
+    l.mrirt_render_brats_ordered.restype = i32
+    l.mrirt_brats_order_applicable.argtypes = l.mrirt_brats_skip_applicable.argtypes
+    l.mrirt_brats_order_applicable.restype = i32
+    l.mrirt_order_build_host.argtypes = [vp, u32, u32, vp]
+    l.mrirt_order_build_host.restype = i32
     l.mrirt_install_abort_trace.argtypes = [i32]
     l.mrirt_install_abort_trace.restype = i32
     l.mrirt_build_cell8.argtypes = [vp, u32, C.POINTER(u32), vp, vp]

@@ -531,6 +531,16 @@ __device__ __forceinline__ void finish(const K1Args& a, int kind, int64_t oidx, 
         wave_count_add(a.stats + 0, r.nLive);
         wave_count_add(a.stats + 1, r.nShaded);
     }
+    if (a.map.steps != nullptr) {                                      // uniform: the dispatch order's step record (k1_order.h)
+        // how long this workgroup held its wave slots: the longest ray of its longest wave, filed under the workgroup's
+        // position in the pixel map (not in the dispatch), so that any order writes the same record.  (The position is a
+        // scalar load away; the logical id behind it is VALU divisions the march would carry in a register to here.)
+        uint32_t v = r.nLive;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v = max(v, (uint32_t)__shfl_xor(v, o));
+        const uint32_t pos = map_position(a.map);
+        if ((threadIdx.x & 63u) == 0 && v != 0u && pos < a.map.chunk * kXcds) atomicMax(a.map.steps + pos, v);
+    }
 }
 
 }  // namespace mrirt

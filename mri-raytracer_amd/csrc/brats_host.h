@@ -19,6 +19,12 @@ int prepare(const MrirtBratsParams* p, const MrirtRenderExt* ext, const void* co
 // mXY, mY, mZ at it.
 int launch_skip_prepass(const MrirtBratsParams* p, const MrirtSkip* skip, bool strict, hipStream_t s, K1Args& a);
 
+// brats_order.hip: the builder of the dispatch order (k1_order.h), launched ahead of a march whose a.map.order / a.map.steps
+// are bound: the table from the record of the last frame, and the record zeroed for this one.  A weak reference: host-only
+// programs that link brats_march.hip without this unit (tests/native/index_harness.hip) still link, and an ordered launch
+// there is refused (MRIRT_ERR_ARG) rather than run without its builder.
+__attribute__((weak)) int launch_order_build(const K1Args& a, uint32_t classes, hipStream_t s);
+
 // brats_slab.hip: the LDS-staged march (VGA layout, one modality, no overlays), selected by brats_march.hip
 int launch_slab_march(const K1Args& a, bool strict, bool shade, hipStream_t s);
 // brats_ring.hip: the plane-synchronous LDS ring march (same launches)

@@ -24,6 +24,7 @@
 // This unit holds the three register-gather march kernels (generic, pipelined, rolling) with the skipping march, the plan
 // that picks one (plan_k1 / launch_plan), prepare() and the K1 entry points.  Its neighbours, joined by brats_host.h:
 //   brats_skip.hip  the pre-pass of exact empty-space skipping (the map's index arithmetic: skip_map.h)
+//   brats_order.hip the builder of the dispatch order: long workgroups first, by the steps the last frames recorded (k1_order.h)
 //   brats_c5.hip    C5, the per-sample INR render (sample counting, emission, the chunked passes)
 //   brats_slab.hip, brats_ring.hip  the LDS marches the plan can select
 //
@@ -33,6 +34,7 @@
 #include <type_traits>
 #include "brats_host.h"
 #include "skip_map.h"
+#include "k1_order.h"
 
 namespace mrirt {
 
@@ -679,6 +681,34 @@ static int launch_plan(const K1Plan& pl, const K1Args& a, hipStream_t s) {
     return MRIRT_OK;
 }
 
+// the workgroup size and the XCD banding of a K1 launch: prepare()'s pixel map, and what mrirt_order_words sizes the
+// dispatch-order tables by
+static int k1_pixel_map(PixelMap& m, const uint32_t imageSize[2], const MrirtRenderExt* ext, int64_t pitch_px) {
+    const uint32_t layout = ext ? ext->layout : (uint32_t)MRIRT_LAYOUT_LINEAR;
+    const uint32_t variant = ext ? ext->kernelVariant : 0u;
+    // Workgroup = one 8 x 8 packet (64 threads: a finished packet's wave slot refills at once) — except on VGA grids, where
+    // a 16 x 16 block of four packets measured 3.7 % faster (1.145 -> 1.10 ms at C3: the four waves' lines meet in one L1).
+    // Variant bit 1 flips the choice; the LDS-staged kernel (bit 6) is written for one packet per workgroup.
+    // ... while the launch has enough of them to go round: an eighth of the config-4 frame (one GPU of eight: 2048 workgroups of
+    // 16 x 16 for 1024 resident ones) ends in a long tail of half-idle CUs — 0.616 ms against 0.500 ms with one-packet
+    // workgroups (tools/tile_share_bench.py, profiles/r03_tile_share.txt); from 4096 upwards the big ones win (0.904 vs 0.918).
+    uint64_t blocks16 = (uint64_t)((imageSize[0] + 15u) / 16u) * ((imageSize[1] + 15u) / 16u);
+    if (ext && ext->tileSize != 0 && ext->tileWorld != 0)
+        blocks16 = (uint64_t)mrirt_tiles_for_rank(imageSize[0], imageSize[1], ext->tileSize, ext->tileRank, ext->tileWorld) *
+                   ((ext->tileSize + 15u) / 16u) * ((ext->tileSize + 15u) / 16u);
+    const bool bigBlocks = ((variant & 2u) != 0u) != (layout == MRIRT_LAYOUT_VGA && (variant & (64u | 2048u)) == 0u && blocks16 >= 4096u);
+    // XCD-interleaved bands one workgroup row high by default (8-px bands for 8 x 8 workgroups: config 2 0.606 -> 0.580 ms,
+    // K1 at 512^3 level; variant bit 3: contiguous run per XCD; bits 4-5: 16 / 8 / 32 / 64 px)
+    const uint32_t bandSel = (variant >> 4) & 3u;
+    const uint32_t bandAsked = bandSel == 0 ? (bigBlocks ? 16u : 8u) : bandSel == 1 ? 16u : bandSel == 2 ? 32u : 64u;
+    const uint32_t bandPx = (variant & 8u) ? 0u : bandAsked;
+    return fill_pixel_map(m, imageSize[0], imageSize[1], pitch_px, ext,
+                          bigBlocks ? 16u : 8u, (variant & 1u) ? 0u : 1u, bandPx,
+                          // the per-band shift of the workgroup order (PixelMap::bandShift): config 2 0.591 -> 0.457 ms; on the
+                          // 16-px workgroups of VGA grids it measured 1.3 % slower (C3), so those keep straight bands.  Bit 9 flips it.
+                          ((variant & 512u) == 0u) != bigBlocks);
+}
+
 // kernelVariant (MrirtRenderExt): experiments, 0 = library default; every bit is decoded by prepare(), into K1Args::map, Prepared and
 // K1Args::debugFlags (bits 7-10 -> debugFlags bits 0-3, bit 12 -> debugFlags bit 5, read by the kernels / brats_ring.hip)
 //   bit 0: row-major instead of Morton lane order
@@ -756,27 +786,7 @@ int prepare(const MrirtBratsParams* p, const MrirtRenderExt* ext, const void* co
         for (int k = 0; k < 3; ++k) if (!isfinite(p->U[k]) || !isfinite(p->V[k]) || !isfinite(p->W[k])) return MRIRT_ERR_ARG;
     }
     fill_camera(a.cam, p->eye, p->U, p->V, p->W, p->fovY, p->imageSize[0], p->imageSize[1], ext, false);
-    // Workgroup = one 8 x 8 packet (64 threads: a finished packet's wave slot refills at once) — except on VGA grids, where
-    // a 16 x 16 block of four packets measured 3.7 % faster (1.145 -> 1.10 ms at C3: the four waves' lines meet in one L1).
-    // Variant bit 1 flips the choice; the LDS-staged kernel (bit 6) is written for one packet per workgroup.
-    // ... while the launch has enough of them to go round: an eighth of the config-4 frame (one GPU of eight: 2048 workgroups of
-    // 16 x 16 for 1024 resident ones) ends in a long tail of half-idle CUs — 0.616 ms against 0.500 ms with one-packet
-    // workgroups (tools/tile_share_bench.py, profiles/r03_tile_share.txt); from 4096 upwards the big ones win (0.904 vs 0.918).
-    uint64_t blocks16 = (uint64_t)((p->imageSize[0] + 15u) / 16u) * ((p->imageSize[1] + 15u) / 16u);
-    if (ext && ext->tileSize != 0 && ext->tileWorld != 0)
-        blocks16 = (uint64_t)mrirt_tiles_for_rank(p->imageSize[0], p->imageSize[1], ext->tileSize, ext->tileRank, ext->tileWorld) *
-                   ((ext->tileSize + 15u) / 16u) * ((ext->tileSize + 15u) / 16u);
-    const bool bigBlocks = ((variant & 2u) != 0u) != (layout == MRIRT_LAYOUT_VGA && (variant & (64u | 2048u)) == 0u && blocks16 >= 4096u);
-    // XCD-interleaved bands one workgroup row high by default (8-px bands for 8 x 8 workgroups: config 2 0.606 -> 0.580 ms,
-    // K1 at 512^3 level; variant bit 3: contiguous run per XCD; bits 4-5: 16 / 8 / 32 / 64 px)
-    const uint32_t bandSel = (variant >> 4) & 3u;
-    const uint32_t bandAsked = bandSel == 0 ? (bigBlocks ? 16u : 8u) : bandSel == 1 ? 16u : bandSel == 2 ? 32u : 64u;
-    const uint32_t bandPx = (variant & 8u) ? 0u : bandAsked;
-    int rc = fill_pixel_map(a.map, p->imageSize[0], p->imageSize[1], pitch_px, ext,
-                            bigBlocks ? 16u : 8u, (variant & 1u) ? 0u : 1u, bandPx,
-                            // the per-band shift of the workgroup order (PixelMap::bandShift): config 2 0.591 -> 0.457 ms; on the
-                            // 16-px workgroups of VGA grids it measured 1.3 % slower (C3), so those keep straight bands.  Bit 9 flips it.
-                            ((variant & 512u) == 0u) != bigBlocks);
+    int rc = k1_pixel_map(a.map, p->imageSize, ext, pitch_px);
     if (rc != MRIRT_OK) return rc;
     fill_grid_dims(a.grid, p->dims, (layout == MRIRT_LAYOUT_VGA || mod4) ? (uint32_t)MRIRT_LAYOUT_VG : layout);
     fill_vga_dims(a.vga, p->dims);
@@ -941,10 +951,16 @@ static int plan_render(const MrirtBratsParams* p, const MrirtRenderExt* ext, con
     return pl.status;
 }
 
-extern "C" int mrirt_render_brats_skip(const MrirtBratsParams* p, const MrirtRenderExt* ext,
-                                       const void* const vol[4], const void* labels, const void* preds,
-                                       const MrirtSkip* skip, void* out_rgba, int64_t pitch_px,
-                                       uint64_t* stats_dev, void* stream) {
+// Does a launch of this plan take a dispatch order (MrirtOrder)?  The pipelined and rolling kernels over the whole frame,
+// marching without an empty-radius map: the launches whose workgroups run for as long as their rays are, in rounds.
+static bool order_applies(const K1Plan& pl, const K1Args& a) {
+    return (pl.family == MRIRT_KERNEL_PIPELINED || pl.family == MRIRT_KERNEL_ROLLING) && !pl.skipping && a.map.tileSize == 0;
+}
+
+extern "C" int mrirt_render_brats_ordered(const MrirtBratsParams* p, const MrirtRenderExt* ext,
+                                          const void* const vol[4], const void* labels, const void* preds,
+                                          const MrirtSkip* skip, const MrirtOrder* order, void* out_rgba, int64_t pitch_px,
+                                          uint64_t* stats_dev, void* stream) {
     if (!out_rgba) return MRIRT_ERR_NULL;
     K1Args a;
     K1Plan pl;
@@ -960,7 +976,43 @@ extern "C" int mrirt_render_brats_skip(const MrirtBratsParams* p, const MrirtRen
         if (rcMap != MRIRT_OK) return rcMap;
         a.leap = pl.leap ? 1u : 0u;
     }
+    if (order != nullptr && order_applies(pl, a)) {
+        if (!order->order || !order->steps) return MRIRT_ERR_NULL;
+        if (order->classes > kOrderMaxClasses || (uint64_t)order->words < (uint64_t)a.map.chunk * kXcds) return MRIRT_ERR_ARG;
+        a.map.order = order->order;
+        a.map.steps = order->steps;
+        if (order->classes != 0) {                                           // (0: the caller's own table)
+            if (launch_order_build == nullptr) return MRIRT_ERR_ARG;         // (a program linked without brats_order.hip)
+            const int rcOrder = launch_order_build(a, order->classes, s);    // brats_order.hip
+            if (rcOrder != MRIRT_OK) return rcOrder;
+        }
+    }
     return pl.strict ? launch_plan<true>(pl, a, s) : launch_plan<false>(pl, a, s);
+}
+
+extern "C" int mrirt_render_brats_skip(const MrirtBratsParams* p, const MrirtRenderExt* ext,
+                                       const void* const vol[4], const void* labels, const void* preds,
+                                       const MrirtSkip* skip, void* out_rgba, int64_t pitch_px,
+                                       uint64_t* stats_dev, void* stream) {
+    return mrirt_render_brats_ordered(p, ext, vol, labels, preds, skip, nullptr, out_rgba, pitch_px, stats_dev, stream);
+}
+
+// 1: mrirt_render_brats_ordered with these arguments orders its launch by the scratch it is given; 0: it ignores the scratch
+extern "C" int mrirt_brats_order_applicable(const MrirtBratsParams* p, const MrirtRenderExt* ext, const void* const vol[4],
+                                            const void* labels, const void* preds, const MrirtSkip* skip) {
+    K1Args a;
+    K1Plan pl;
+    const int rc = plan_render(p, ext, vol, labels, preds, skip, p ? (int64_t)p->imageSize[0] : 0, a, pl);
+    if (rc != MRIRT_OK) return rc;
+    return order_applies(pl, a) ? 1 : 0;
+}
+
+// words of MrirtOrder's tables: the workgroups of the untiled launch, padded as the launch pads them (chunk * 8)
+extern "C" int64_t mrirt_order_words(const uint32_t imageSize[2], const MrirtRenderExt* ext) {
+    PixelMap m;
+    if (!imageSize || (ext && ext->tileSize != 0)) return 0;
+    if (k1_pixel_map(m, imageSize, ext, (int64_t)imageSize[0]) != MRIRT_OK) return 0;
+    return (int64_t)m.chunk * kXcds;
 }
 
 extern "C" int mrirt_render_brats_ex(const MrirtBratsParams* p, const MrirtRenderExt* ext,

@@ -337,6 +337,11 @@ struct PixelMap {
     uint32_t bandBlocks;               // whole-frame XCD interleave: workgroups per band (0 = contiguous runs)
     uint32_t bandShift;                // whole frame: an XCD's j-th band starts bandShift * j workgroups further along x (mod blocksX)
     int64_t  pitch;                    // pixels per output row (whole-frame mode)
+    // dispatch order (k1_order.h; null = workgroup b marches position b).  order[b] is the position workgroup b marches: a
+    // permutation of 0 .. chunk * 8 - 1 that keeps b % 8, so every workgroup stays on the XCD the hardware dealt it to.
+    // steps[position]: the march kernels' record of the longest wave's step count per workgroup (finish(), brats_device.h)
+    const uint32_t* order;
+    uint32_t* steps;
 };
 
 // Workgroups are dealt round-robin over the 8 XCDs (b % 8 = XCD group), so logical id
@@ -355,7 +360,9 @@ MRIRT_HD uint32_t tile_dealt_index(uint32_t tx, uint32_t ty, uint32_t tilesX, ui
     return ty * tilesX + (tx + tilesX - (skew * ty) % tilesX) % tilesX;
 }
 
-MRIRT_HD int map_pixel_at(const PixelMap& m, uint32_t b, uint32_t tid, uint32_t& px, uint32_t& py, int64_t& outIndex) {
+// position b (a workgroup index of the launch, or what the order table put in its place) -> logical id: row-major over the
+// workgroups of the whole frame, or over the compact buffer's in tile mode; >= numBlocks: no pixels
+MRIRT_HD uint32_t map_logical(const PixelMap& m, uint32_t b) {
     uint32_t logical;
     if (m.bandBlocks != 0) {
         // whole frame: horizontal bands of bandBlocks workgroups (a few packet rows) dealt round-robin
@@ -373,6 +380,11 @@ MRIRT_HD int map_pixel_at(const PixelMap& m, uint32_t b, uint32_t tid, uint32_t&
     } else {
         logical = (b % kXcds) * m.chunk + b / kXcds;     // one contiguous run per XCD
     }
+    return logical;
+}
+
+MRIRT_HD int map_pixel_at(const PixelMap& m, uint32_t b, uint32_t tid, uint32_t& px, uint32_t& py, int64_t& outIndex) {
+    const uint32_t logical = map_logical(m, b);
     if (logical >= m.numBlocks) return 0;
     uint32_t wave = tid >> 6, lane = tid & 63u;
     uint32_t lx, ly;
@@ -402,8 +414,12 @@ MRIRT_HD int map_pixel_at(const PixelMap& m, uint32_t b, uint32_t tid, uint32_t&
     }
     return (px < m.width && py < m.height) ? 1 : 0;
 }
+// the position this workgroup marches (wave-uniform: a scalar load where a table is bound)
+__device__ __forceinline__ uint32_t map_position(const PixelMap& m) {
+    return m.order != nullptr ? m.order[blockIdx.x] : blockIdx.x;
+}
 __device__ __forceinline__ int map_pixel(const PixelMap& m, uint32_t& px, uint32_t& py, int64_t& outIndex) {
-    return map_pixel_at(m, blockIdx.x, threadIdx.x, px, py, outIndex);
+    return map_pixel_at(m, map_position(m), threadIdx.x, px, py, outIndex);
 }
 
 // RGBA store, fp32 or the reference's rgba16_float

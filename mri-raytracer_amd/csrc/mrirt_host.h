@@ -80,6 +80,7 @@ inline int fill_pixel_map(PixelMap& m, uint32_t width, uint32_t height, int64_t 
                           uint32_t blockPx = kBlockPx, uint32_t laneOrder = 0, uint32_t bandPx = 0, bool shiftBands = false) {
     if (width == 0 || height == 0) return MRIRT_ERR_DIMS;
     m.width = width; m.height = height; m.pitch = pitch;
+    m.order = nullptr; m.steps = nullptr;
     m.tileSize = ext ? ext->tileSize : 0u;
     m.tileRank = ext ? ext->tileRank : 0u;
     m.tileWorld = ext ? ext->tileWorld : 0u;

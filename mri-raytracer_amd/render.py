@@ -316,7 +316,9 @@ def kernel_family(params: Mapping[str, Any], ext: Optional[Mapping[str, Any]] = 
     "label_cells": bool}``.  The generic kernel is the fall-back with 64-bit offsets: VG / QUAD grids >= 4 GiB, label grids
     >= 2^30 elements, LINEAR grids >= 2^30 voxels, BRICK grids, shaded LINEAR."""
     P = brats_params(params)
-    E = render_ext(dict(ext or {}))
+    ext = dict(ext or {})
+    ext.pop("order", None)                # (render_brats's switch: no field of MrirtRenderExt)
+    E = render_ext(ext)
     fake = C.c_void_p(0x1000)
     vp = (C.c_void_p * 4)(*[fake if (P.volEnabled[m] != 0 or int(E.layout) == _lib.LAYOUT_MOD4) else None for m in range(4)])
     S = None
@@ -432,6 +434,57 @@ def _bind_skip(P, E, vp, lab, prd, intensities, labels, preds, dev, stream):
     return S, entry, hold
 
 
+ORDER_DEFAULT = True        # render_brats orders eligible launches unless ext["order"] says otherwise
+ORDER_CLASSES = 4           # MrirtOrder.classes: length classes per XCD (profiles/r18_order: 2 / 4 / 8 / 16 swept)
+ORDER_REBUILD_EVERY = 8     # frames between two runs of the builder kernel on a scratch (the first two frames always run it)
+ORDER_MAP_BITS = 0xA7B      # the kernelVariant bits that shape the pixel map (lane order aside): 0, 1, 3, 4-5, 6, 9, 11
+_ORDERS: "collections.OrderedDict[tuple, list]" = collections.OrderedDict()      # key -> [scratch tensor, frames launched with it]
+_ORDERS_MAX = 16
+order_binds = 0             # how many launches went out with a dispatch order (tests)
+
+
+def _bind_order(P, E, vp, lab, prd, S, pitch, dev, stream):
+    """MrirtOrder for one call, or (None, None) when the library does not order this launch (``mrirt_brats_order_applicable``:
+    host-only).  The scratch — the order table and the step record the march writes for the next frame's table — is cached
+    like ``_bind_skip`` caches maps: allocated with the launch stream current, one per (device, stream, image size, pitch,
+    table size = workgroup size, the map bits of ``kernelVariant``), so frames in flight on different streams never share
+    a record.  The camera is not part of the key: the record of the last frames predicts this one, and a stale prediction
+    costs time, never a pixel.
+
+    The builder kernel and the stream's wait between it and the march cost about 12 us of a 1 ms frame, half of what the
+    order gains (profiles/r18_order), and a table built from the frame eight frames ago is as good as one from the last:
+    so the builder runs on a scratch's first two frames (the second has the first's record) and then on every
+    ``ORDER_REBUILD_EVERY``-th; the frames between march by the standing table (``classes = 0``) while the record keeps the
+    per-workgroup maximum over them."""
+    global order_binds
+    lib = _lib.lib()
+    rc = int(lib.mrirt_brats_order_applicable(C.byref(P), C.byref(E), vp, _ptr(lab), _ptr(prd), C.byref(S) if S is not None else None))
+    if rc < 0:
+        _lib.check(rc, "mrirt_brats_order_applicable")
+    size = (C.c_uint32 * 2)(int(P.imageSize[0]), int(P.imageSize[1]))
+    words = int(lib.mrirt_order_words(size, C.byref(E)))
+    if rc == 0 or words == 0:
+        return None, None
+    ts = _as_stream(stream)
+    key = (dev.index, int(ts.cuda_stream), int(P.imageSize[0]), int(P.imageSize[1]), int(pitch), words, int(E.layout),
+           int(E.kernelVariant) & ORDER_MAP_BITS)
+    entry = _ORDERS.get(key)
+    if entry is None:
+        entry = _ORDERS[key] = [torch.zeros(2 * words, dtype=torch.int32, device=dev), 0]     # [order | steps]: a zero record = identity
+        while len(_ORDERS) > _ORDERS_MAX:
+            _ORDERS.popitem(last=False)             # (stream-ordered by the allocator, as _SkipMap's tensors)
+    else:
+        _ORDERS.move_to_end(key)
+    t, frame = entry
+    entry[1] = frame + 1
+    O = _lib.Order()
+    O.order, O.steps = t.data_ptr(), t.data_ptr() + 4 * words
+    O.words = words
+    O.classes = ORDER_CLASSES if frame < 2 or frame % max(1, ORDER_REBUILD_EVERY) == 0 else 0
+    order_binds += 1
+    return O, t
+
+
 def render_brats(params: Mapping[str, Any], intensities: Sequence[Optional[Union[ArrayLike, Grid]]],
                  labels: Optional[Union[ArrayLike, Grid]] = None, preds: Optional[Union[ArrayLike, Grid]] = None,
                  out: Optional[torch.Tensor] = None, ext: Optional[Mapping[str, Any]] = None,
@@ -447,8 +500,13 @@ def render_brats(params: Mapping[str, Any], intensities: Sequence[Optional[Union
     ``Grid`` objects carrying their macro-cell summaries, i.e. made by ``upload_grid``): samples in 8^3 macro
     cells that cannot contribute under this call's window, weights and overlays composite nothing, and the packet
     crosses wide empty regions in leaps sized by an empty-radius map of those cells.
+
+    ``ext["order"]`` (default ``ORDER_DEFAULT``): dispatch the launch's workgroups longest first by the step counts the
+    previous frame on this stream recorded (``_bind_order``; same bits, same counters); ``False`` for A/B runs.
     """
     dev = _require_gpu()
+    ext = dict(ext or {})
+    ordered = bool(ext.pop("order", ORDER_DEFAULT))
     # every temporary of this call (uploads of host arrays, the output, the counters, the skip mask) is made on
     # the launch stream, so the kernels are ordered after their producers and the caching allocator ties the
     # memory to that stream
@@ -464,7 +522,16 @@ def render_brats(params: Mapping[str, Any], intensities: Sequence[Optional[Union
         S = entry = hold = None
         if skip:
             S, entry, hold = _bind_skip(P, E, vp, lab, prd, intensities, labels, preds, dev, stream)
-        if S is not None:
+        O = otab = None
+        if ordered:
+            O, otab = _bind_order(P, E, vp, lab, prd, S, pitch, dev, stream)
+        if O is not None:
+            rc = _lib.lib().mrirt_render_brats_ordered(C.byref(P), C.byref(E), vp, _ptr(lab), _ptr(prd), C.byref(S) if S is not None else None,
+                                                       C.byref(O), _ptr(o), pitch, _ptr(st), _stream_ptr(stream))
+            _lib.check(rc, "mrirt_render_brats_ordered")
+            if entry is not None:
+                entry.built = True
+        elif S is not None:
             rc = _lib.lib().mrirt_render_brats_skip(C.byref(P), C.byref(E), vp, _ptr(lab), _ptr(prd), C.byref(S), _ptr(o),
                                                     pitch, _ptr(st), _stream_ptr(stream))
             _lib.check(rc, "mrirt_render_brats_skip")
@@ -476,7 +543,7 @@ def render_brats(params: Mapping[str, Any], intensities: Sequence[Optional[Union
         if stats:
             s = st.cpu()
             return o, {"live_samples": int(s[0]), "shaded_samples": int(s[1])}
-        del hold                                    # (only here: every launch that reads these tensors has been enqueued)
+        del hold, otab                              # (only here: every launch that reads these tensors has been enqueued)
     return o
 
 
