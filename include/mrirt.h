@@ -44,7 +44,9 @@ extern "C" {
  *    the extended loss and the tumour-ratio sampler: MrirtInrLossExt, MrirtInrTumourIndex, MrirtInrTrainExt
  *    (mrirt_sizeof(13..15)), mrirt_inr_loss_ext_scratch_bytes, mrirt_inr_loss_ext, mrirt_inr_tumour_count,
  *    mrirt_inr_tumour_index_scratch_bytes, mrirt_inr_tumour_index, mrirt_inr_sample_batch_mix,
- *    mrirt_inr_train_run_ext_scratch_bytes, mrirt_inr_train_run_ext. */
+ *    mrirt_inr_train_run_ext_scratch_bytes, mrirt_inr_train_run_ext;
+ *    case preparation (no new struct): mrirt_prep_scratch_bytes, mrirt_prep_window, mrirt_prep_normalize,
+ *    mrirt_prep_zscore_scratch_bytes, mrirt_prep_zscore_stats, mrirt_prep_zscore_apply, mrirt_prep_gaussian3d. */
 #define MRIRT_ABI_VERSION 4
 
 typedef enum MrirtStatus {
@@ -872,6 +874,50 @@ int mrirt_render_brats_inr(const MrirtBratsParams* params, const MrirtRenderExt*
                            const void* labels, const MrirtInrDesc* net, const float zmu[4], const float zsigma[4],
                            uint32_t chunk_steps, void* scratch, int64_t scratch_bytes,
                            void* out_rgba, int64_t pitch_px, uint64_t* stats_dev, void* stream);
+
+/* ------------------------------------------------------------------------------------ */
+/* Case preparation: percentile window, normalisation, z-score, Gaussian pre-filter      */
+/* ------------------------------------------------------------------------------------ */
+/* What the reference does to a case on the host before any kernel sees it (inr/viewer/brats_viewer.py:46-65,281-287,
+ * scripts/jax_inr_brats.py:266-270), with the same results bit for bit.  Every pointer but `weights` is a device pointer;
+ * each call is a chain of launches on `stream`, nothing synchronises with the host, and two calls on the same data give the
+ * same bits (integer atomics only; every fp64 sum is taken in an order fixed by n).
+ *
+ * Window: np.percentile(vol, q) of n fp32 values, default method `linear`, as NumPy evaluates it for fp32 data — with
+ * s = sort(vol) (NaN last, -0.0 == +0.0) and every operation a separate fp32 one:
+ *   v = f32(n - 1) * (f32(q) / f32(100));  k = floor(v) (at most n - 1);  g = v - f32(k)
+ *   a = s[k];  b = s[min(k + 1, n - 1)];  d = b - a;   p = g < 0.5 ? a + d * g : b - d * (1 - g);   NaN if vol holds a NaN
+ * record (8 floats) = { lo, hi, span, min, max, p_lo, p_hi, 0 }: (lo, hi) = (p_lo, p_hi), or (min, max) when p_hi <= p_lo;
+ * span = f32(max(1e-6, double(hi) - double(lo))) (1e-6 when the difference is NaN).
+ * Limits (checked before any HIP call): 1 <= n <= 2^31 - 1, 0 <= q_lo, q_hi <= 100, scratch 16-byte aligned and at least
+ * mrirt_prep_scratch_bytes(n) bytes (MRIRT_ERR_ARG).  mrirt_prep_scratch_bytes: with B = min(ceil(n / 4096), 512) histogram blocks,
+ * 256 B of state + 8 B per block (rounded up to 256 B) + 4096 B of totals + 4096 B per block; 0 for n outside the limits. */
+int64_t mrirt_prep_scratch_bytes(int64_t n);
+int mrirt_prep_window(const float* vol, int64_t n, float q_lo, float q_hi, float* record, void* scratch, int64_t scratch_bytes,
+                      void* stream);
+/* clip((v - lo) / span, 0, 1) in fp32 (correctly rounded division; NaN stays NaN) with lo = record[0], span = record[2] read on
+ * the device.  vol: [X][Y][Z] C order, dims = { X, Y, Z }.  norm (may be NULL; may be vol): the same order.  linear (may be
+ * NULL; not vol): the x-fastest buffer of the K1 grids, index x + y X + z X Y.  At least one output; X Y Z <= 2^31 - 1. */
+int mrirt_prep_normalize(const float* vol, const uint32_t dims[3], const float* record, float* norm, float* linear, void* stream);
+/* Z-score over the non-zero voxels of num_mods (1..64) volumes of n values each, mods = [num_mods][n]:
+ *   count = #(v != 0);  mu = sum(v) / count;  sigma = sqrt(sum((v - mu)^2) / count)   over v != 0, in fp64
+ *   stats (4 num_mods 32-bit words) = { f32 mu[num_mods], f32 sigma[num_mods], f32 divisor[num_mods], u32 count[num_mods] }
+ *   with divisor = f32(sigma) + f32(1e-6): mu and divisor are the zmu / zsigma of mrirt_render_brats_inr, which divides by
+ *   zsigma as given.
+ *   apply: out = (v - mu) / divisor in fp32 for every voxel, zeros included; a volume with count == 0 is copied unchanged.
+ *   out may be mods.
+ * scratch: 16-byte aligned, mrirt_prep_zscore_scratch_bytes(n, num_mods) bytes; 0 for arguments outside the limits. */
+int64_t mrirt_prep_zscore_scratch_bytes(int64_t n, uint32_t num_mods);
+int mrirt_prep_zscore_stats(const float* mods, int64_t n, uint32_t num_mods, void* stats, void* scratch, int64_t scratch_bytes,
+                            void* stream);
+int mrirt_prep_zscore_apply(const float* mods, int64_t n, uint32_t num_mods, const void* stats, float* out, void* stream);
+/* scipy.ndimage.gaussian_filter on an fp32 C-order volume, mode `reflect`: axes 0, 1, 2 in that order, each pass in unfused
+ * fp64 stored as fp32:  t = x[i] w[r];  for j = -r .. -1:  t += (x[i + j] + x[i - j]) w[j + r];  an index outside the axis
+ * reflects as m = i mod 2n, m < n ? m : 2n - 1 - m.  weights: HOST array of 2 radius + 1 doubles (SciPy's: exp(-0.5 x^2 /
+ * sigma^2) over its sum, radius = int(4 sigma + 0.5)), read during the call; 0 <= radius <= 16 (MRIRT_ERR_ARG).  out may be
+ * vol; scratch is one more volume of the same size; any other overlap is MRIRT_ERR_ARG. */
+int mrirt_prep_gaussian3d(const float* vol, const uint32_t dims[3], const double* weights, int32_t radius, float* out,
+                          float* scratch, void* stream);
 
 /* ------------------------------------------------------------------------------------ */
 /* Misc                                                                                  */

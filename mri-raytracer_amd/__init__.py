@@ -10,7 +10,8 @@ the task-mandated name ``mri-raytracer_amd``.  Layout:
   mesh.py     K4: PLY loading, the reference's BVH, upload + validation, render_mesh; class surfaces of label volumes
   shim.py     slangpy-shaped ``Device`` / ``ComputeKernel.dispatch(thread_count, vars, ...)``
   camera.py   OrbitalCamera (both reference variants)
-  volume.py   load-time volume preparation (normalise, flatten, world frame, u8 pack, BC4)
+  volume.py   load-time volume preparation (normalise, flatten, world frame, u8 pack, BC4) and the same on the device
+              (normalize_intensity_device, zscore_nonzero_device, gaussian_filter_device: csrc/prep.hip)
   inr.py      model_load / build_input / apply_mlp / predict_volume on the MFMA MLP kernel
   tiles.py    image-tile sharding + RCCL framebuffer gather (one process per GPU)
   synth.py    deterministic synthetic scenes for tests and bench
@@ -18,10 +19,11 @@ the task-mandated name ``mri-raytracer_amd``.  Layout:
 from . import _lib, camera, grad, inr, mesh, nifti, params, render, shim, soft, synth, tiles, torch_ops, viewer, volume  # noqa: F401
 from .camera import OrbitalCamera  # noqa: F401
 from .grad import render_brats_autograd, render_brats_backward  # noqa: F401
-from .inr import apply_mlp, build_input, inr_forward, model_load, predict_volume, render_brats_inr  # noqa: F401
+from .inr import apply_mlp, build_input, inr_forward, model_load, predict_volume, prepare_case, render_brats_inr  # noqa: F401
 from .mesh import (build_bvh, extract_surface, load_ply, normalize_mesh, render_mesh, surface_mesh,  # noqa: F401
                    upload_mesh)
 from .shim import Device, KernelShim  # noqa: F401
+from .volume import gaussian_filter_device, normalize_intensity_device, zscore_nonzero_device  # noqa: F401
 from .soft import render_brats_soft, render_brats_soft_autograd, render_brats_soft_backward  # noqa: F401
 from .render import (Grid, detile, render_brats, render_sdf, render_volume_u8, tiles_for_rank,  # noqa: F401
                      unbrick_grid, upload_grid, upload_label_cells, upload_mod4)

@@ -17,7 +17,7 @@ CSRC = PKG_DIR / "csrc"
 INCLUDE = PKG_DIR.parent / "include"
 SO_PATH = pathlib.Path(os.environ.get("MRIRT_LIB", PKG_DIR / "libmrirt.so"))   # override: A/B builds in development
 HIP_SOURCES = ["brats_march.hip", "brats_order.hip", "brats_skip.hip", "brats_c5.hip", "brats_slab.hip", "brats_ring.hip", "brats_backward.hip", "brats_soft.hip", "volume_march.hip", "grid_ops.hip", "inr_mlp.hip",
-               "inr_stream.hip", "inr_ws.hip", "inr_refine.hip", "inr_train.hip", "inr_optim.hip", "inr_muon.hip", "inr_lossx.hip", "mesh_rt.hip", "edt.hip", "surface.hip", "abort_trace.cpp"]
+               "inr_stream.hip", "inr_ws.hip", "inr_refine.hip", "inr_train.hip", "inr_optim.hip", "inr_muon.hip", "inr_lossx.hip", "mesh_rt.hip", "edt.hip", "surface.hip", "prep.hip", "abort_trace.cpp"]
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17", "-Wall"]
 
 # every extern "C" symbol include/mrirt.h declares
@@ -42,6 +42,8 @@ ABI_SYMBOLS = [
     "mrirt_inr_loss_ext_scratch_bytes", "mrirt_inr_loss_ext", "mrirt_inr_tumour_count", "mrirt_inr_tumour_index_scratch_bytes",
     "mrirt_inr_tumour_index", "mrirt_inr_sample_batch_mix", "mrirt_inr_train_run_ext_scratch_bytes", "mrirt_inr_train_run_ext",
     "mrirt_order_words", "mrirt_render_brats_ordered", "mrirt_brats_order_applicable", "mrirt_order_build_host",
+    "mrirt_prep_scratch_bytes", "mrirt_prep_window", "mrirt_prep_normalize", "mrirt_prep_zscore_scratch_bytes",
+    "mrirt_prep_zscore_stats", "mrirt_prep_zscore_apply", "mrirt_prep_gaussian3d",
 ]
 
 ABI_VERSION = 4          # MRIRT_ABI_VERSION of include/mrirt.h this binding was written against
@@ -450,6 +452,20 @@ def lib() -> C.CDLL:
     l.mrirt_inr_train_run_ext.argtypes = [C.POINTER(InrDesc), C.POINTER(InrCache), C.POINTER(InrTrainCfg), C.POINTER(InrTrainExt),
                                           C.POINTER(InrTrainState), u64, u32, vp, vp, i64, vp]
     l.mrirt_inr_train_run_ext.restype = i32
+    l.mrirt_prep_scratch_bytes.argtypes = [i64]
+    l.mrirt_prep_scratch_bytes.restype = i64
+    l.mrirt_prep_window.argtypes = [vp, i64, f32, f32, vp, vp, i64, vp]
+    l.mrirt_prep_window.restype = i32
+    l.mrirt_prep_normalize.argtypes = [vp, C.POINTER(u32), vp, vp, vp, vp]
+    l.mrirt_prep_normalize.restype = i32
+    l.mrirt_prep_zscore_scratch_bytes.argtypes = [i64, u32]
+    l.mrirt_prep_zscore_scratch_bytes.restype = i64
+    l.mrirt_prep_zscore_stats.argtypes = [vp, i64, u32, vp, vp, i64, vp]
+    l.mrirt_prep_zscore_stats.restype = i32
+    l.mrirt_prep_zscore_apply.argtypes = [vp, i64, u32, vp, vp, vp]
+    l.mrirt_prep_zscore_apply.restype = i32
+    l.mrirt_prep_gaussian3d.argtypes = [vp, C.POINTER(u32), C.POINTER(C.c_double), i32, vp, vp, vp]
+    l.mrirt_prep_gaussian3d.restype = i32
     l.mrirt_status_string.argtypes = [i32]
     l.mrirt_status_string.restype = C.c_char_p
     l.mrirt_sizeof.argtypes = [u32]

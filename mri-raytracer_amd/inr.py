@@ -214,18 +214,47 @@ def siren_apply(params, x, w0: float = 30.0, net: Optional[PackedMLP] = None) ->
 
 
 def predict_volume(params, case_data: Dict[str, Any], fourier_freqs: int, chunk: int = 200000,
-                   net: Optional[PackedMLP] = None):
+                   net: Optional[PackedMLP] = None, prefilter_sigma: Optional[float] = None):
     """model.py:119-141: argmax class per voxel of ``case_data["mods"]`` (M,H,W,D) -> int16 (H,W,D).
-    ``chunk`` is accepted for signature parity; the kernel streams the whole volume in one launch."""
+    ``chunk`` is accepted for signature parity; the kernel streams the whole volume in one launch.
+    ``prefilter_sigma``: every modality first goes through scipy.ndimage.gaussian_filter(mods[m], sigma) on the device
+    (volume.gaussian_filter_device, bit for bit); 0.5 is what scripts/jax_inr_brats.py:266-270 applies."""
     dev = _require_gpu()
     mods = _dev_f32(case_data["mods"], dev)
     M, H, W, D = mods.shape
+    if prefilter_sigma is not None:
+        from . import volume
+        filtered = torch.empty_like(mods)
+        for m in range(M):
+            volume.gaussian_filter_device(mods[m], prefilter_sigma, out=filtered[m])
+        mods = filtered
     net = net or pack_mlp(params, KIND_FOURIER_RELU, fourier_freqs, M)
     pred = torch.empty((H, W, D), dtype=torch.int16, device=dev)
     hwd = (C.c_uint32 * 3)(H, W, D)
     rc = _lib.lib().mrirt_inr_predict_volume(C.byref(net.desc), _ptr(mods), hwd, _ptr(pred), _stream_ptr(None))
     _lib.check(rc, "mrirt_inr_predict_volume")
     return pred, case_data["seg"]
+
+
+def prepare_case(mods_raw, seg=None, remap_label4: bool = True) -> Dict[str, Any]:
+    """A raw case -> the dict VoxelCache, predict_volume and evaluate_single_case take, prepared on the device
+    (dataloader.load_case / jax_inr_brats._load_case without the host): ``mods`` the (M, H, W, D) modalities z-scored over
+    their non-zero voxels (volume.zscore_nonzero_device), ``seg`` the int16 labels with 4 -> 3 (``None`` stays ``None``),
+    ``zstats`` the device (4, M) record { mu, sigma, sigma + 1e-6, count bits } (volume.zscore_constants reads it)."""
+    from . import volume
+    dev = _require_gpu()
+    m = mods_raw if isinstance(mods_raw, torch.Tensor) else np.asarray(mods_raw, dtype=np.float32)
+    if m.ndim != 4:
+        raise ValueError(f"mods_raw: expected (M, H, W, D), got shape {tuple(m.shape)}")
+    z, stats = volume.zscore_nonzero_device(m)
+    lab = None
+    if seg is not None:
+        lab = _label_volume(seg, dev, "seg")
+        if tuple(lab.shape) != tuple(z.shape[1:]):
+            raise ValueError(f"seg has shape {tuple(lab.shape)}, the modalities {tuple(z.shape[1:])}")
+        if remap_label4:
+            lab = torch.where(lab == 4, torch.full_like(lab, 3), lab)
+    return {"mods": z, "seg": lab, "zstats": stats}
 
 
 def _label_counts(pred, true, num_classes: int):

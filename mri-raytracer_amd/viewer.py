@@ -50,7 +50,8 @@ def save_png(path, rgba: np.ndarray) -> None:
 
 
 class BraTSViewer:
-    def __init__(self, case_dir: Optional[pathlib.Path] = None, up: str = "Y", layout: str = "auto", math_mode: str = "strict"):
+    def __init__(self, case_dir: Optional[pathlib.Path] = None, up: str = "Y", layout: str = "auto", math_mode: str = "strict",
+                 prep: str = "host"):
         self.device = shim.Device(enable_debug_layers=True, layout=layout, math=math_mode)
         program = self.device.load_program("brats_rt.slang", ["brats_main"])
         self.kernel = self.device.create_compute_kernel(program)
@@ -75,7 +76,7 @@ class BraTSViewer:
         self._empty_float = self._create_buffer(np.zeros(1, dtype=np.float32))
         self._empty_uint = self._create_buffer(np.zeros(1, dtype=np.uint32))
         if case_dir is not None:
-            self.load_dir(pathlib.Path(case_dir))
+            self.load_dir(pathlib.Path(case_dir), prep=prep)
 
     def _create_buffer(self, linear: np.ndarray) -> shim.Buffer:
         b = self.device.create_buffer(element_count=linear.size, struct_size=4, usage=shim.BufferUsage.shader_resource)
@@ -83,20 +84,33 @@ class BraTSViewer:
         return b
 
     # -- loading ---------------------------------------------------------------------------
-    def load_arrays(self, mods: Dict[str, np.ndarray], zooms=(1.0, 1.0, 1.0), seg: Optional[np.ndarray] = None) -> None:
-        """The body of load_dir for in-memory (X,Y,Z) arrays keyed by 'T1n','T1c','T2w','FLAIR'."""
+    def _adopt_buffer(self, linear: torch.Tensor) -> shim.Buffer:
+        b = shim.Buffer(self.device, linear.numel(), 4)
+        b.tensor = linear.to(self.device.torch_device)
+        b._version += 1
+        return b
+
+    def load_arrays(self, mods: Dict[str, np.ndarray], zooms=(1.0, 1.0, 1.0), seg: Optional[np.ndarray] = None, prep: str = "host") -> None:
+        """The body of load_dir for in-memory (X,Y,Z) arrays keyed by 'T1n','T1c','T2w','FLAIR'.  ``prep="device"``: the window
+        and the normalisation run on the GPU (volume.normalize_intensity_device, the same bits); the buffers and
+        ``raw_volumes`` are then device tensors and ``load_inr`` z-scores them there."""
+        if prep not in ("host", "device"):
+            raise ValueError(f"prep must be 'host' or 'device', got {prep!r}")
         if not mods:
             raise RuntimeError("none of the four modality volumes (t1 / t1ce / t2 / flair) could be loaded")
         dims = None
         self.raw_volumes, self.buffers = {}, {k: self._empty_float for k in MOD_ORDER}
         for key, data in mods.items():
-            lin, norm, d = volume.normalize_intensity(data)
+            if prep == "device":
+                lin, norm, d, _ = volume.normalize_intensity_device(data)
+            else:
+                lin, norm, d = volume.normalize_intensity(data)
             if dims is None:
                 dims = d
             elif not np.all(d == dims):
                 raise RuntimeError(f"modality {key} has dims {tuple(int(v) for v in d)}, the others {tuple(int(v) for v in dims)}")
             self.raw_volumes[key] = norm          # the viewer keeps the NORMALISED array (brats_viewer.py:205,218,227)
-            self.buffers[key] = self._create_buffer(lin)
+            self.buffers[key] = self._adopt_buffer(lin) if prep == "device" else self._create_buffer(lin)
         self.vol_dims = dims.astype(np.uint32)
         self.voxel_size, self.vol_min, _, _ = volume.world_frame(dims, zooms)
         self.seg_buffer = None
@@ -107,7 +121,7 @@ class BraTSViewer:
         self.pred_buffer, self.show_pred = None, False
         self.frame_volume()
 
-    def load_dir(self, case_dir: pathlib.Path) -> None:
+    def load_dir(self, case_dir: pathlib.Path, prep: str = "host") -> None:
         mods, seg, zooms = {}, None, None
         for f in sorted(pathlib.Path(case_dir).glob("*.nii.gz")):
             name = f.name.lower()
@@ -121,7 +135,7 @@ class BraTSViewer:
                     zooms = z if zooms is None else zooms
         if not mods:
             raise RuntimeError("none of the four modality volumes (t1 / t1ce / t2 / flair) could be loaded")
-        self.load_arrays(mods, zooms, seg)
+        self.load_arrays(mods, zooms, seg, prep=prep)
 
     def frame_volume(self) -> None:
         if self.vol_dims is None:
@@ -141,7 +155,10 @@ class BraTSViewer:
         k = int(cfg.get("FOURIER_FREQS", cfg.get("fourier_freqs", 10)))
         if not all(m in self.raw_volumes for m in MOD_ORDER):
             raise RuntimeError("the INR prepass needs all four modalities loaded")
-        mods = np.stack([volume.zscore_nonzero(self.raw_volumes[m]) for m in MOD_ORDER], axis=0)
+        if all(isinstance(self.raw_volumes[m], torch.Tensor) for m in MOD_ORDER):          # loaded with prep="device"
+            mods, _ = volume.zscore_nonzero_device(torch.stack([self.raw_volumes[m] for m in MOD_ORDER], dim=0))
+        else:
+            mods = np.stack([volume.zscore_nonzero(self.raw_volumes[m]) for m in MOD_ORDER], axis=0)
         pred, _ = inr_model.predict_volume(params, {"mods": mods, "seg": None}, fourier_freqs=k)
         self.pred_buffer = shim.Buffer(self.device, pred.numel(), 4)
         self.pred_buffer.tensor = inr_model.labels_for_viewer(pred)

@@ -6,6 +6,8 @@ Mirrors (array-in/array-out, no NIfTI dependency):
   * u8 packing, NIfTI-mask mapping and the BC4 block decode —
     scripts/volumeRendering/app.py:145-250
 These run once per case on the host (as in the reference); per-frame work is all on the GPU.
+The ``*_device`` functions at the end are the same preparation on the GPU (csrc/prep.hip): the percentile window
+and normalisation, the z-score and scipy.ndimage's Gaussian filter, bit for bit what the host definitions give.
 """
 from __future__ import annotations
 
@@ -133,3 +135,139 @@ def zscore_nonzero(arr: np.ndarray) -> np.ndarray:
     if nz.any():
         a = (a - a[nz].mean()) / (a[nz].std() + 1e-6)
     return a
+
+
+# --- the same preparation on the GPU (csrc/prep.hip) ----------------------------------------------------------------------
+GAUSS_MAX_RADIUS = 16
+
+
+def _device_f32(x):
+    """NumPy array or tensor -> contiguous fp32 tensor on the GPU (a device fp32 tensor is used as it is)."""
+    import torch
+    if not torch.cuda.is_available():
+        raise RuntimeError("the *_device preparation needs an MI355X; the functions without the suffix are the host code")
+    if not isinstance(x, torch.Tensor):
+        a = np.ascontiguousarray(x, dtype=np.float32)
+        x = torch.from_numpy(a if a.flags.writeable else a.copy())
+    t = x
+    return t.to(device="cuda", dtype=torch.float32).contiguous()
+
+
+def _stream(stream):
+    import ctypes as C
+    import torch
+    return C.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
+
+
+def _ptr(t):
+    import ctypes as C
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _dims3(shape):
+    import ctypes as C
+    return (C.c_uint32 * 3)(*[int(v) for v in shape])
+
+
+def prep_window_device(vol, percentiles=(1.0, 99.5), stream=None):
+    """The window record of a volume, on the device: 8 floats { lo, hi, span, min, max, p_lo, p_hi, 0 } with p = np.percentile
+    (fp32, ``linear``) and the min / max fallback of :func:`normalize_intensity`.  Nothing is read back."""
+    import torch
+    from . import _lib
+    t = _device_f32(vol)
+    n = t.numel()
+    l = _lib.lib()
+    need = l.mrirt_prep_scratch_bytes(n)
+    if need == 0:
+        raise ValueError(f"a volume of {n} values is outside 1 .. 2^31 - 1")
+    scratch = torch.empty(need, dtype=torch.uint8, device=t.device)
+    record = torch.empty(8, dtype=torch.float32, device=t.device)
+    _lib.check(l.mrirt_prep_window(_ptr(t), n, float(percentiles[0]), float(percentiles[1]), _ptr(record), _ptr(scratch), need,
+                                   _stream(stream)), "mrirt_prep_window")
+    return record
+
+
+def normalize_intensity_device(data, percentiles=(1.0, 99.5), stream=None):
+    """:func:`normalize_intensity` on the GPU: (X,Y,Z) raw intensities (NumPy or device tensor) -> (linear, norm, dims,
+    window); ``linear`` (x fastest) and ``norm`` (X,Y,Z) are device fp32 tensors equal to the host function's arrays,
+    ``dims`` the same uint32 array, ``window`` the device record of :func:`prep_window_device`."""
+    import torch
+    from . import _lib
+    t = _device_f32(data)
+    if t.dim() != 3:
+        raise ValueError(f"expected an (X,Y,Z) volume, got shape {tuple(t.shape)}")
+    window = prep_window_device(t, percentiles, stream)
+    norm = torch.empty_like(t)
+    linear = torch.empty(t.numel(), dtype=torch.float32, device=t.device)
+    _lib.check(_lib.lib().mrirt_prep_normalize(_ptr(t), _dims3(t.shape), _ptr(window), _ptr(norm), _ptr(linear), _stream(stream)),
+               "mrirt_prep_normalize")
+    return linear, norm, np.asarray(t.shape, dtype=np.uint32), window
+
+
+def zscore_nonzero_device(mods, out=None, stream=None):
+    """:func:`zscore_nonzero` of every modality on the GPU.  ``mods``: (M, ...) — each ``mods[m]`` is z-scored on its own —
+    or one 3-D volume.  Returns (z, stats): ``z`` a device fp32 tensor of the input's shape (``out=mods`` works in place),
+    ``stats`` a device fp32 (4, M) tensor { mu, sigma, sigma + 1e-6, count (its uint32 bits) }: rows 0 and 2 are the
+    ``zmu`` / ``zsigma`` that render_brats_inr and render_brats_inr_autograd take (they divide by zsigma as given, so it is
+    the row WITH the 1e-6).  mu and sigma come from fp64 sums in a fixed order."""
+    import torch
+    from . import _lib
+    t = _device_f32(mods)
+    single = t.dim() == 3
+    M = 1 if single else int(t.shape[0])
+    if t.dim() < 2 or M < 1:
+        raise ValueError(f"expected (M, ...) modalities or one volume, got shape {tuple(t.shape)}")
+    n = t.numel() // M
+    l = _lib.lib()
+    need = l.mrirt_prep_zscore_scratch_bytes(n, M)
+    if need == 0:
+        raise ValueError(f"{M} modalities of {n} values are outside the limits (1..64 modalities of 1 .. 2^31 - 1 values)")
+    scratch = torch.empty(need, dtype=torch.uint8, device=t.device)
+    stats = torch.empty((4, M), dtype=torch.float32, device=t.device)
+    z = torch.empty_like(t) if out is None else out
+    if z.shape != t.shape or z.dtype != torch.float32 or not z.is_cuda or not z.is_contiguous():
+        raise ValueError("out must be a contiguous device fp32 tensor of the input's shape")
+    s = _stream(stream)
+    _lib.check(l.mrirt_prep_zscore_stats(_ptr(t), n, M, _ptr(stats), _ptr(scratch), need, s), "mrirt_prep_zscore_stats")
+    _lib.check(l.mrirt_prep_zscore_apply(_ptr(t), n, M, _ptr(stats), _ptr(z), s), "mrirt_prep_zscore_apply")
+    return z, stats
+
+
+def zscore_constants(stats):
+    """Host copies of a stats record: (zmu, zsigma, count) with zsigma = sigma + 1e-6, the divisor the INR renders expect."""
+    h = stats.detach().cpu().numpy()
+    return h[0].copy(), h[2].copy(), h[3].view(np.uint32).copy()
+
+
+def gaussian_weights(sigma: float) -> np.ndarray:
+    """SciPy's Gaussian kernel for ``sigma``: radius int(4 sigma + 0.5), exp(-0.5 / sigma^2 x^2) over its sum, NumPy fp64."""
+    sigma = float(sigma)
+    if not (sigma > 0.0 and np.isfinite(sigma)):
+        raise ValueError(f"sigma must be positive and finite, got {sigma}")
+    r = int(4.0 * sigma + 0.5)
+    if r > GAUSS_MAX_RADIUS:
+        raise ValueError(f"sigma {sigma} needs radius {r} > {GAUSS_MAX_RADIUS}")
+    x = np.arange(-r, r + 1)
+    w = np.exp(-0.5 / (sigma * sigma) * x ** 2)
+    return w / w.sum()
+
+
+def gaussian_filter_device(vol, sigma, out=None, stream=None):
+    """scipy.ndimage.gaussian_filter(vol, sigma) (fp32, mode ``reflect``) of a 3-D volume on the GPU, bit for bit.
+    ``out`` may be ``vol`` itself (a device tensor) for an in-place filter."""
+    import ctypes as C
+    import torch
+    from . import _lib
+    t = _device_f32(vol)
+    if t.dim() != 3:
+        raise ValueError(f"expected a 3-D volume, got shape {tuple(t.shape)}")
+    w = gaussian_weights(sigma)
+    r = (len(w) - 1) // 2
+    res = torch.empty_like(t) if out is None else out
+    if res.shape != t.shape or res.dtype != torch.float32 or not res.is_cuda or not res.is_contiguous():
+        raise ValueError("out must be a contiguous device fp32 tensor of the input's shape")
+    scratch = torch.empty_like(t)
+    wc = (C.c_double * len(w))(*w.tolist())
+    _lib.check(_lib.lib().mrirt_prep_gaussian3d(_ptr(t), _dims3(t.shape), wc, r, _ptr(res), _ptr(scratch), _stream(stream)),
+               "mrirt_prep_gaussian3d")
+    return res
