@@ -46,7 +46,9 @@ extern "C" {
  *    mrirt_inr_tumour_index_scratch_bytes, mrirt_inr_tumour_index, mrirt_inr_sample_batch_mix,
  *    mrirt_inr_train_run_ext_scratch_bytes, mrirt_inr_train_run_ext;
  *    case preparation (no new struct): mrirt_prep_scratch_bytes, mrirt_prep_window, mrirt_prep_normalize,
- *    mrirt_prep_zscore_scratch_bytes, mrirt_prep_zscore_stats, mrirt_prep_zscore_apply, mrirt_prep_gaussian3d. */
+ *    mrirt_prep_zscore_scratch_bytes, mrirt_prep_zscore_stats, mrirt_prep_zscore_apply, mrirt_prep_gaussian3d;
+ *    connected components (no new struct): mrirt_cc_scratch_bytes, mrirt_cc_label, mrirt_cc_sizes, mrirt_cc_filter,
+ *    mrirt_slice_counts. */
 #define MRIRT_ABI_VERSION 4
 
 typedef enum MrirtStatus {
@@ -782,6 +784,37 @@ int mrirt_surface_count(const int16_t* labels, const uint32_t hwd[3], uint32_t c
 int mrirt_surface_extract(const int16_t* labels, const uint32_t hwd[3], uint32_t class_mask, const float spacing[3],
                           const float origin[3], float* verts, int64_t vert_cap, int32_t* tris, int64_t tri_cap,
                           void* scratch, int64_t scratch_bytes, int64_t* counts_dev, void* stream);
+
+/* ------------------------------------------------------------------------------------ */
+/* Connected components of label volumes; the counts of the slice-consistency score     */
+/* ------------------------------------------------------------------------------------ */
+/* labels: the int16 [n0][n1][n2] C-order volume of mrirt_surface_* (device), with the same inside rule: voxel v is inside iff
+ * 0 <= labels[v] < 32 and bit labels[v] of class_mask is set; a voxel outside the volume is outside.  Two inside voxels are
+ * adjacent iff they differ by at most 1 on every axis and on at most `connectivity` (1, 2 or 3) axes: the 6, 18 or 26
+ * neighbours, scipy.ndimage.generate_binary_structure(3, connectivity).  A component is a class of the transitive closure;
+ * its root is its smallest linear index (i0 n1 + i1) n2 + i2, and components are numbered 1 .. N by increasing root — the
+ * numbering of scipy.ndimage.label.
+ * Limits (checked before any HIP call): every extent >= 1 (MRIRT_ERR_DIMS); n0 n1 n2 <= 2^31 - 1, connectivity in 1..3,
+ * 0 <= n_components <= n0 n1 n2, min_voxels >= 0, keep_largest 0 or 1, scratch 16-byte aligned and scratch_bytes large
+ * enough (MRIRT_ERR_ARG).  Nothing synchronises with the host; every result is the same from run to run.
+ * mrirt_cc_scratch_bytes: device bytes mrirt_cc_label needs (4 B per 1024 voxels, and per 1024 of those until one such
+ * chunk is left, each part rounded up to 256 B); 0 for a volume outside the limits. */
+int64_t mrirt_cc_scratch_bytes(const uint32_t hwd[3]);
+/* components (device, int32 [n0][n1][n2]) = the component number of every inside voxel, 0 outside; it is the call's working
+ * array and every element is written.  count_dev (device, int64[1]) = N. */
+int mrirt_cc_label(const int16_t* labels, const uint32_t hwd[3], uint32_t class_mask, uint32_t connectivity,
+                   int32_t* components, int64_t* count_dev /* [1] = N */, void* scratch, int64_t scratch_bytes, void* stream);
+/* sizes (device, int32 [n_components]): sizes[k - 1] = voxels of component k.  Numbers outside 1 .. n_components are not
+ * counted; n_components == 0 accepts a NULL sizes and does nothing. */
+int mrirt_cc_sizes(const int32_t* components, const uint32_t hwd[3], int64_t n_components, int32_t* sizes, void* stream);
+/* out[v] = labels[v] where components[v] is 0 (or outside 1 .. n_components) or v's component is kept, else fill.  A
+ * component is kept iff its size >= min_voxels and, with keep_largest, it is the largest one (ties: the lowest number).
+ * out may be labels. */
+int mrirt_cc_filter(const int16_t* labels, const int32_t* components, const int32_t* sizes, int64_t n_components,
+                    const uint32_t hwd[3], int64_t min_voxels, int32_t keep_largest, int16_t fill, int16_t* out, void* stream);
+/* counts (device, int64 [n2][3]) = { A, I, U } per index z of the LAST axis, on the raw int16 values p: A = #(p_z > 0);
+ * for z >= 1, I = #((p_z == p_{z-1}) & (p_z > 0)) and U = #((p_z > 0) | (p_{z-1} > 0)); I = U = 0 at z = 0. */
+int mrirt_slice_counts(const int16_t* labels, const uint32_t hwd[3], int64_t* counts /* [n2][3] = A, I, U */, void* stream);
 
 /* ------------------------------------------------------------------------------------ */
 /* K1 backward: frame gradients to voxel grids and transfer-function parameters         */

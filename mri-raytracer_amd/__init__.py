@@ -8,6 +8,7 @@ the task-mandated name ``mri-raytracer_amd``.  Layout:
   grad.py     K1 backward: render_brats_backward, render_brats_autograd (frame gradients to voxels and window / level)
   soft.py     the soft prediction overlay: render_brats_soft, its backward and render_brats_soft_autograd (frame gradients to logits)
   mesh.py     K4: PLY loading, the reference's BVH, upload + validation, render_mesh; class surfaces of label volumes
+  components.py  connected components of label volumes, their sizes, small-component removal, slice counts (csrc/components.hip)
   shim.py     slangpy-shaped ``Device`` / ``ComputeKernel.dispatch(thread_count, vars, ...)``
   camera.py   OrbitalCamera (both reference variants)
   volume.py   load-time volume preparation (normalise, flatten, world frame, u8 pack, BC4) and the same on the device
@@ -16,10 +17,11 @@ the task-mandated name ``mri-raytracer_amd``.  Layout:
   tiles.py    image-tile sharding + RCCL framebuffer gather (one process per GPU)
   synth.py    deterministic synthetic scenes for tests and bench
 """
-from . import _lib, camera, grad, inr, mesh, nifti, params, render, shim, soft, synth, tiles, torch_ops, viewer, volume  # noqa: F401
+from . import _lib, camera, components, grad, inr, mesh, nifti, params, render, shim, soft, synth, tiles, torch_ops, viewer, volume  # noqa: F401
 from .camera import OrbitalCamera  # noqa: F401
+from .components import component_sizes, label_components, remove_small_components, slice_counts  # noqa: F401
 from .grad import render_brats_autograd, render_brats_backward  # noqa: F401
-from .inr import apply_mlp, build_input, inr_forward, model_load, predict_volume, prepare_case, render_brats_inr  # noqa: F401
+from .inr import apply_mlp, build_input, compute_multi_metrics, inr_forward, model_load, predict_volume, prepare_case, render_brats_inr  # noqa: F401
 from .mesh import (build_bvh, extract_surface, load_ply, normalize_mesh, render_mesh, surface_mesh,  # noqa: F401
                    upload_mesh)
 from .shim import Device, KernelShim  # noqa: F401

@@ -17,7 +17,7 @@ CSRC = PKG_DIR / "csrc"
 INCLUDE = PKG_DIR.parent / "include"
 SO_PATH = pathlib.Path(os.environ.get("MRIRT_LIB", PKG_DIR / "libmrirt.so"))   # override: A/B builds in development
 HIP_SOURCES = ["brats_march.hip", "brats_order.hip", "brats_skip.hip", "brats_c5.hip", "brats_slab.hip", "brats_ring.hip", "brats_backward.hip", "brats_soft.hip", "volume_march.hip", "grid_ops.hip", "inr_mlp.hip",
-               "inr_stream.hip", "inr_ws.hip", "inr_refine.hip", "inr_train.hip", "inr_optim.hip", "inr_muon.hip", "inr_lossx.hip", "mesh_rt.hip", "edt.hip", "surface.hip", "prep.hip", "abort_trace.cpp"]
+               "inr_stream.hip", "inr_ws.hip", "inr_refine.hip", "inr_train.hip", "inr_optim.hip", "inr_muon.hip", "inr_lossx.hip", "mesh_rt.hip", "edt.hip", "surface.hip", "prep.hip", "components.hip", "abort_trace.cpp"]
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17", "-Wall"]
 
 # every extern "C" symbol include/mrirt.h declares
@@ -44,6 +44,7 @@ ABI_SYMBOLS = [
     "mrirt_order_words", "mrirt_render_brats_ordered", "mrirt_brats_order_applicable", "mrirt_order_build_host",
     "mrirt_prep_scratch_bytes", "mrirt_prep_window", "mrirt_prep_normalize", "mrirt_prep_zscore_scratch_bytes",
     "mrirt_prep_zscore_stats", "mrirt_prep_zscore_apply", "mrirt_prep_gaussian3d",
+    "mrirt_cc_scratch_bytes", "mrirt_cc_label", "mrirt_cc_sizes", "mrirt_cc_filter", "mrirt_slice_counts",
 ]
 
 ABI_VERSION = 4          # MRIRT_ABI_VERSION of include/mrirt.h this binding was written against
@@ -466,6 +467,16 @@ def lib() -> C.CDLL:
     l.mrirt_prep_zscore_apply.restype = i32
     l.mrirt_prep_gaussian3d.argtypes = [vp, C.POINTER(u32), C.POINTER(C.c_double), i32, vp, vp, vp]
     l.mrirt_prep_gaussian3d.restype = i32
+    l.mrirt_cc_scratch_bytes.argtypes = [C.POINTER(u32)]
+    l.mrirt_cc_scratch_bytes.restype = i64
+    l.mrirt_cc_label.argtypes = [vp, C.POINTER(u32), u32, u32, vp, vp, vp, i64, vp]
+    l.mrirt_cc_label.restype = i32
+    l.mrirt_cc_sizes.argtypes = [vp, C.POINTER(u32), i64, vp, vp]
+    l.mrirt_cc_sizes.restype = i32
+    l.mrirt_cc_filter.argtypes = [vp, vp, vp, i64, C.POINTER(u32), i64, i32, C.c_int16, vp, vp]
+    l.mrirt_cc_filter.restype = i32
+    l.mrirt_slice_counts.argtypes = [vp, C.POINTER(u32), vp, vp]
+    l.mrirt_slice_counts.restype = i32
     l.mrirt_status_string.argtypes = [i32]
     l.mrirt_status_string.restype = C.c_char_p
     l.mrirt_sizeof.argtypes = [u32]

@@ -301,6 +301,44 @@ def coverage_dice(pred, true) -> float:
     return (2 * int(h[1, 1]) + 1e-6) / (denom + 1e-6) if denom > 0 else 0.0
 
 
+def compute_multi_metrics(pred, true, num_classes: int = 4) -> Dict[str, Any]:
+    """notebooks/improved.ipynb's evaluation of a predicted volume, with its keys and its expressions:
+    ``dice_class_{c}`` = (2 |P_c & T_c| + 1e-6) / (|P_c| + |T_c| + 1e-6), **0.0** (not NaN) for a class in neither volume;
+    ``n_components_class_{c}`` for c = 1 .. num_classes - 1, the 6-connected components of ``pred == c`` (0 for an absent
+    class; ``scipy.ndimage.label``'s count); ``slice_consistency``, the mean over the indices z >= 1 of the last axis with
+    U > 0 of 2 I / (U + A[z] + A[z-1] + 1e-6) (``components.slice_counts``), 0.0 when there is none.
+    A tensor prediction (what ``predict_volume`` returns) is evaluated on the device — the components by csrc/components.hip,
+    the sums as integers, only those read back — and a NumPy prediction on the host, without a GPU."""
+    from . import components
+    n = int(num_classes)
+    h = _label_counts(pred, true, n)
+    out: Dict[str, Any] = {}
+    for c in range(n):
+        union = int(h[c, :].sum()) + int(h[:, c].sum())
+        out[f"dice_class_{c}"] = (2 * int(h[c, c]) + 1e-6) / (union + 1e-6) if union > 0 else 0.0
+    if isinstance(pred, torch.Tensor):
+        dev = pred.device if pred.is_cuda else _require_gpu()
+        lab = _label_volume(pred, dev, "pred")
+        for c in range(1, n):
+            out[f"n_components_class_{c}"] = components.label_components(lab, c, 1)[1]
+        counts = components.slice_counts(lab).cpu().numpy()
+    else:
+        p = np.asarray(pred)
+        if p.ndim != 3:
+            raise ValueError(f"pred: expected an (H, W, D) volume, got shape {p.shape}")
+        for c in range(1, n):
+            out[f"n_components_class_{c}"] = components.count_components_host(p == c, 1)
+        pos = p > 0
+        counts = np.zeros((p.shape[2], 3), dtype=np.int64)
+        counts[:, 0] = pos.sum(axis=(0, 1))
+        counts[1:, 1] = ((p[:, :, 1:] == p[:, :, :-1]) & pos[:, :, 1:]).sum(axis=(0, 1))
+        counts[1:, 2] = (pos[:, :, 1:] | pos[:, :, :-1]).sum(axis=(0, 1))
+    ratios = [np.float64(2 * int(i)) / (int(u) + int(a) + int(a_prev) + 1e-6)
+              for (a, i, u), a_prev in zip(counts[1:].tolist(), counts[:-1, 0].tolist()) if u > 0]
+    out["slice_consistency"] = float(np.mean(ratios)) if ratios else 0.0
+    return out
+
+
 def _label_volume(x, dev, what: str) -> torch.Tensor:
     """A label volume (NumPy array or tensor, any integer dtype or bool) as the contiguous int16 (H, W, D) device tensor the
     kernels read.  A value that int16 cannot hold is no class's label: it becomes -1 instead of wrapping into one."""
