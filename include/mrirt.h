@@ -901,7 +901,16 @@ int mrirt_render_brats_soft_backward(const MrirtBratsParams* params, const Mrirt
  *              (58 B per pixel per step of a pass + 64 B per pixel + 12 KiB: 1.5 GB for 512 x 512 x 96)
  *   stats_dev: optional, THREE device uint64 counters, atomically incremented by
  *              {composited (live) samples, gradient-shaded samples, MLP queries}
- * The frame is bit-identical to mrirt_brats_sample_counts / _emit_samples / mrirt_render_brats_stream run over whole rays (the MLP is batch-position invariant). */
+ * The frame is bit-identical to mrirt_brats_sample_counts / _emit_samples / mrirt_render_brats_stream run over whole rays (the MLP is batch-position invariant).
+ * Refused before anything is enqueued or written (besides the checks every K1 entry point shares):
+ *   MRIRT_ERR_NULL    params, vol (or a vol[m]; MOD4: vol[0]), net, its weights or biases, zmu, zsigma, scratch or out_rgba is
+ *                     NULL; showSeg without labels
+ *   MRIRT_ERR_LAYOUT  a label-cell binding, VGA voxels, gradient shading with QUAD or MOD4 voxels
+ *   MRIRT_ERR_ARG     tiles; a net that is not Fourier/ReLU or SIREN over four modalities or that mrirt_inr_pack_bytes refuses;
+ *                     showPred == 0; chunk_steps outside 1..4096; width x height x chunk_steps >= 2^32 - 2^21;
+ *                     scratch_bytes too small; more than 1024 passes (box diagonal / stepSize, stretched by the fp32 drift of
+ *                     t += stepSize, over chunk_steps)
+ * mrirt_brats_inr_scratch_bytes returns 0 for a chunk_steps or an image it refuses. */
 int64_t mrirt_brats_inr_scratch_bytes(const MrirtBratsParams* params, uint32_t chunk_steps);
 int mrirt_render_brats_inr(const MrirtBratsParams* params, const MrirtRenderExt* ext, const void* const vol[4],
                            const void* labels, const MrirtInrDesc* net, const float zmu[4], const float zsigma[4],

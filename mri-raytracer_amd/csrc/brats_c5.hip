@@ -399,12 +399,16 @@ static int c5_carve(const MrirtBratsParams* p, uint32_t chunk, void* base, C5Scr
     return MRIRT_OK;
 }
 
+// the C5 passes read LINEAR / BRICK / VG / QUAD / MOD4 grids; QUAD and MOD4 carry no gradients
+static bool c5_layout_ok(uint32_t layout, bool shade) {
+    const bool flat = layout == MRIRT_LAYOUT_QUAD || layout == MRIRT_LAYOUT_MOD4;
+    return (layout <= MRIRT_LAYOUT_QUAD || layout == MRIRT_LAYOUT_MOD4) && !(flat && shade);
+}
+
 template <bool STRICT>
 static int c5_launch_plan(const K1Args& a, const EmitArgs& e, uint32_t layout, bool shade, const C5Scratch& sc, uint32_t pass,
                           uint32_t chunk, hipStream_t s) {
-    // the C5 passes read LINEAR / BRICK / VG / QUAD / MOD4 grids; QUAD and MOD4 carry no gradients
-    const bool flat = layout == MRIRT_LAYOUT_QUAD || layout == MRIRT_LAYOUT_MOD4;
-    if ((layout > MRIRT_LAYOUT_QUAD && layout != MRIRT_LAYOUT_MOD4) || (flat && shade)) return MRIRT_ERR_LAYOUT;
+    if (!c5_layout_ok(layout, shade)) return MRIRT_ERR_LAYOUT;
     uint32_t* counter = sc.counters + pass;
     if (pass == 0) {                                                  // later passes are planned by the composite kernel
         hipLaunchKernelGGL(c5_plan_kernel, dim3(a.map.chunk * kXcds), dim3(a.map.blockPx == 8 ? 64 : 256), 0, s,
@@ -451,11 +455,15 @@ extern "C" int mrirt_render_brats_inr(const MrirtBratsParams* p, const MrirtRend
     for (int m = 0; m < (mod4 ? 1 : 4); ++m) if (!vol[m]) return MRIRT_ERR_NULL;     // the MLP reads all four modalities
     if (ext && ext->tileSize != 0) return MRIRT_ERR_ARG;                      // whole-frame only
     if ((net->kind != MRIRT_INR_FOURIER_RELU && net->kind != MRIRT_INR_SIREN) || net->numMods != 4) return MRIRT_ERR_ARG;
+    // what inr_forward_dev_n would refuse in the first pass, after the plan and the emission had written the scratch
+    if (mrirt_inr_pack_bytes(net) <= 0) return MRIRT_ERR_ARG;
+    if (!net->weights || !net->biases) return MRIRT_ERR_NULL;
     K1Args a;
     Prepared cfg;
     int rc = prepare(p, ext, vol, labels, nullptr, true, pitch_px, a, cfg);
     if (rc != MRIRT_OK) return rc;
     if (a.labCell != nullptr) return MRIRT_ERR_LAYOUT;           // the C5 passes read the ground-truth grid themselves (LINEAR / BRICK)
+    if (!c5_layout_ok(cfg.layout, cfg.shade)) return MRIRT_ERR_LAYOUT;       // refused before anything touches the scratch
     if (p->showPred == 0) return MRIRT_ERR_ARG;
     C5Scratch sc;
     rc = c5_carve(p, chunk_steps, scratch, sc);
