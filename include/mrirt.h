@@ -152,7 +152,12 @@ typedef struct MrirtRenderExt {
     /* Image-tile sharding (one process per GPU).  tileSize == 0: whole image into
      * out[y*pitch + x].  Otherwise this call renders the tiles t with t % tileWorld ==
      * tileRank (t = ty*tilesX + tx, tiles of tileSize^2 pixels) into a COMPACT buffer
-     * out[local_tile][tileSize][tileSize][4]; pitch is ignored.                            */
+     * out[local_tile][tileSize][tileSize][4]; pitch is ignored.  Slots of an edge tile that
+     * lie outside the image hold the background (K1: bgColor, K2: 0; alpha 1).  A rank that
+     * owns no tile (mrirt_tiles_for_rank == 0: tileWorld larger than the number of tiles)
+     * launches nothing, counts nothing and returns MRIRT_OK, and since its compact buffer
+     * is empty, out_rgba may be NULL for it in the K1 entry points and mrirt_render_volume:
+     * a NULL out_rgba is MRIRT_ERR_NULL only where the call has at least one block to write. */
     uint32_t tileSize, tileRank, tileWorld;
     uint32_t kernelVariant;     /* 0 = library default; others select experimental kernels (bench/tests) */
     /* Tile sharding, load balance: the dealt tile t sits at row ty = t / tilesX, column tx = (t % tilesX + tileSkew * ty) % tilesX

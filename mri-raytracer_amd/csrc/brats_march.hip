@@ -961,11 +961,12 @@ extern "C" int mrirt_render_brats_ordered(const MrirtBratsParams* p, const Mrirt
                                           const void* const vol[4], const void* labels, const void* preds,
                                           const MrirtSkip* skip, const MrirtOrder* order, void* out_rgba, int64_t pitch_px,
                                           uint64_t* stats_dev, void* stream) {
-    if (!out_rgba) return MRIRT_ERR_NULL;
     K1Args a;
     K1Plan pl;
     const int rc = plan_render(p, ext, vol, labels, preds, skip, pitch_px, a, pl);
     if (rc != MRIRT_OK) return rc;
+    // (a rank that owns no tile has no block to write: its compact buffer is empty, and an empty buffer has no address)
+    if (!out_rgba && a.map.numBlocks != 0) return MRIRT_ERR_NULL;
     a.out = out_rgba;
     a.stats = stats_dev;
     hipStream_t s = static_cast<hipStream_t>(stream);

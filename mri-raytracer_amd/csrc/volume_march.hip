@@ -244,7 +244,7 @@ extern "C" int mrirt_build_cell8(const void* voxels, uint32_t src_mode, const ui
 
 extern "C" int mrirt_render_volume(const MrirtVolumeParams* p, const MrirtRenderExt* ext, const void* volume,
                                    uint32_t mode, void* out_rgba, int64_t pitch_px, uint64_t* stats_dev, void* stream) {
-    if (!p || !volume || !out_rgba) return MRIRT_ERR_NULL;
+    if (!p || !volume) return MRIRT_ERR_NULL;
     if (mode > MRIRT_VOX_CELL8) return MRIRT_ERR_LAYOUT;
     for (int k = 0; k < 3; ++k) if (p->volDim[k] < 1) return MRIRT_ERR_DIMS;
     if ((uint64_t)p->volDim[0] * p->volDim[1] * p->volDim[2] >= (1ull << 32)) return MRIRT_ERR_DIMS;
@@ -259,6 +259,8 @@ extern "C" int mrirt_render_volume(const MrirtVolumeParams* p, const MrirtRender
     // 16x16-pixel workgroups, one workgroup row per band, bands interleaved over the XCDs (load balance)
     int rc = fill_pixel_map(a.map, p->imageSize[0], p->imageSize[1], pitch_px, ext, kBlockPx, 0, kBlockPx);
     if (rc != MRIRT_OK) return rc;
+    // (a rank that owns no tile has no block to write: its compact buffer is empty, and an empty buffer has no address)
+    if (!out_rgba && a.map.numBlocks != 0) return MRIRT_ERR_NULL;
     for (int k = 0; k < 3; ++k) { a.dim[k] = p->volDim[k]; a.dimM1[k] = (float)p->volDim[k] - 1.0f; }
     a.nearP = fmaxf(0.0f, p->nearPlane);
     a.farP = fmaxf(a.nearP, p->farPlane);

@@ -432,7 +432,8 @@ def test_shim_k2_marches_the_cell8_copy():
     assert np.array_equal(frames[0], frames[1]) and frames[0][..., 0].max() > 0.05
 
 
-@pytest.mark.parametrize("layout", ["vg", "vga"])          # vga (16 x 16-pixel workgroups) is what bench.py --gpus N marches
+@pytest.mark.parametrize("layout", ["vg", "vga"])          # vga is what bench.py --gpus N marches: a rank's 2048 16 x 16 blocks are below
+                                                           # the 4096 of k1_pixel_map, so both layouts take 64-thread (8 x 8) workgroups here
 def test_c4_full_size_tiles_over_eight_ranks(env, layout):
     """BASELINE config 4 at full size on one GPU: 512^3, 2048 x 2048, 512 steps, shaded, 64 x 64 tiles dealt to 8
     'ranks'.  Each rank's compact tile buffer, gathered and de-tiled (the HIP de-tiling kernel), must be the
