@@ -191,6 +191,33 @@ int mrirt_render_brats_ex(const MrirtBratsParams* params, const MrirtRenderExt* 
                           const void* const vol[4], const void* labels, const void* preds,
                           void* out_rgba, int64_t pitch_px, uint64_t* stats_dev, void* stream);
 
+/* K1 with an RGBA transfer-function table (build-defined extension).  Same arguments and checks as
+ * mrirt_render_brats_ex, plus the table: tf_rgba = tf_entries rows of (r, g, b, sigma) fp32 in DEVICE memory, 16-byte
+ * aligned, 2 <= tf_entries <= 1024.  Window, level and gamma stay as the table's domain mapping: everything up to
+ *   val = pow(saturate((v - (wl - ww/2)) / ww), gamma)                   (brats_rt.slang:132-133)
+ * is the plain march; then per sample, with N = tf_entries (STRICT: unfused fp32 in this order; FAST may contract):
+ *   u = val * float(N-1);  i = min(uint(floor(u)), N-2);  f = u - float(i)
+ *   e[k] = tf[i][k] + f * (tf[i+1][k] - tf[i][k]), k = 0..3;  sigma = e[3];  the sample counts as live
+ *   if sigma > 0:  alpha = 1 - exp(-(sigma * intensityAlpha) * stepSize)      (the full-range exp: sigma may exceed 1)
+ *                  C[k] += (alpha * T) * (e[k] * shade);  T *= 1 - alpha       (shade = 1 unless shadeMode = 1)
+ * Label overlays, t += stepSize and the loop test are unchanged.  The two-entry ramp (0,0,0,0), (1,1,1,1) gives e[k] = val:
+ * the frame and the counters of mrirt_render_brats_ex, bit for bit (STRICT).
+ *   Intensity layouts: LINEAR, BRICK, VG, VGA shaded or not, 1-4 modalities; QUAD and MOD4 unshaded only (MRIRT_ERR_LAYOUT
+ *   with shading, as mrirt_render_brats_ex).  Label layouts: LINEAR, BRICK, LABCELL.  Both cameras, ertOverride, rgba16f
+ *   output, tile sharding with tileSkew, STRICT and FAST.
+ *   stats_dev (optional) = {live samples, gradient-shaded samples with sigma > 0}.
+ *   Refused with nothing launched: tf_rgba NULL -> MRIRT_ERR_NULL; tf_entries < 2 or > 1024, a table that is not 16-byte
+ *   aligned, kernelVariant bits other than bit 1 (workgroup flip) and bit 2 -> MRIRT_ERR_ARG.
+ *   kernelVariant bit 2 means "the generic table kernel" here: without it MOD4 unshaded launches (overlays off or through
+ *   label cells) and VGA shaded one-modality launches without overlays take a software-pipelined table kernel (STRICT: for
+ *   gamma == 1; grids below 4 GiB) — the same frame and counters, bit for bit.
+ * There is no empty-space skipping (it would need the largest sigma over a cell's val range), no dispatch order and no
+ * class stream with a table.                                                                                            */
+int mrirt_render_brats_tf(const MrirtBratsParams* params, const MrirtRenderExt* ext, const void* const vol[4],
+                          const void* labels, const void* preds,
+                          const float* tf_rgba, uint32_t tf_entries,
+                          void* out_rgba, int64_t pitch_px, uint64_t* stats_dev, void* stream);
+
 /* Host CPU twin? No: the product has no CPU fallback.  The CPU restatement lives in oracle/. */
 
 /* Per-sample INR query along the rays (build-defined, BASELINE config 5): the label

@@ -5,6 +5,7 @@ the task-mandated name ``mri-raytracer_amd``.  Layout:
   csrc/       hand-written gfx950 HIP kernels + the C ABI (include/mrirt.h) -> libmrirt.so
   _lib.py     ctypes binding (fails loudly when the library is missing — no CPU fallback)
   render.py   render_brats / render_volume_u8 / render_sdf over device tensors
+  transfer.py RGBA transfer-function tables for render_brats(tf=...): tf_ramp, tf_from_points, tf_preset
   grad.py     K1 backward: render_brats_backward, render_brats_autograd (frame gradients to voxels and window / level)
   soft.py     the soft prediction overlay: render_brats_soft, its backward and render_brats_soft_autograd (frame gradients to logits)
   mesh.py     K4: PLY loading, the reference's BVH, upload + validation, render_mesh; class surfaces of label volumes
@@ -17,7 +18,8 @@ the task-mandated name ``mri-raytracer_amd``.  Layout:
   tiles.py    image-tile sharding + RCCL framebuffer gather (one process per GPU)
   synth.py    deterministic synthetic scenes for tests and bench
 """
-from . import _lib, camera, components, grad, inr, mesh, nifti, params, render, shim, soft, synth, tiles, torch_ops, viewer, volume  # noqa: F401
+from . import _lib, camera, components, grad, inr, mesh, nifti, params, render, shim, soft, synth, tiles, torch_ops, transfer, viewer, volume  # noqa: F401
+from .transfer import tf_from_points, tf_preset, tf_ramp  # noqa: F401
 from .camera import OrbitalCamera  # noqa: F401
 from .components import component_sizes, label_components, remove_small_components, slice_counts  # noqa: F401
 from .grad import render_brats_autograd, render_brats_backward  # noqa: F401

@@ -16,7 +16,7 @@ PKG_DIR = pathlib.Path(__file__).resolve().parent
 CSRC = PKG_DIR / "csrc"
 INCLUDE = PKG_DIR.parent / "include"
 SO_PATH = pathlib.Path(os.environ.get("MRIRT_LIB", PKG_DIR / "libmrirt.so"))   # override: A/B builds in development
-HIP_SOURCES = ["brats_march.hip", "brats_order.hip", "brats_skip.hip", "brats_c5.hip", "brats_slab.hip", "brats_ring.hip", "brats_backward.hip", "brats_soft.hip", "volume_march.hip", "grid_ops.hip", "inr_mlp.hip",
+HIP_SOURCES = ["brats_march.hip", "brats_order.hip", "brats_skip.hip", "brats_c5.hip", "brats_slab.hip", "brats_ring.hip", "brats_backward.hip", "brats_soft.hip", "brats_tf.hip", "volume_march.hip", "grid_ops.hip", "inr_mlp.hip",
                "inr_stream.hip", "inr_ws.hip", "inr_refine.hip", "inr_train.hip", "inr_optim.hip", "inr_muon.hip", "inr_lossx.hip", "mesh_rt.hip", "edt.hip", "surface.hip", "prep.hip", "components.hip", "abort_trace.cpp"]
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17", "-Wall"]
 
@@ -45,6 +45,7 @@ ABI_SYMBOLS = [
     "mrirt_prep_scratch_bytes", "mrirt_prep_window", "mrirt_prep_normalize", "mrirt_prep_zscore_scratch_bytes",
     "mrirt_prep_zscore_stats", "mrirt_prep_zscore_apply", "mrirt_prep_gaussian3d",
     "mrirt_cc_scratch_bytes", "mrirt_cc_label", "mrirt_cc_sizes", "mrirt_cc_filter", "mrirt_slice_counts",
+    "mrirt_render_brats_tf",
 ]
 
 ABI_VERSION = 4          # MRIRT_ABI_VERSION of include/mrirt.h this binding was written against
@@ -312,6 +313,8 @@ def lib() -> C.CDLL:
     vp, i64, i32 = C.c_void_p, C.c_int64, C.c_int
     l.mrirt_render_brats.argtypes = [C.POINTER(BratsParams), C.POINTER(vp), vp, vp, vp, i64, vp]
     l.mrirt_render_brats_ex.argtypes = [C.POINTER(BratsParams), C.POINTER(RenderExt), C.POINTER(vp), vp, vp, vp, i64, vp, vp]
+    l.mrirt_render_brats_tf.argtypes = [C.POINTER(BratsParams), C.POINTER(RenderExt), C.POINTER(vp), vp, vp, vp, u32, vp, i64, vp, vp]
+    l.mrirt_render_brats_tf.restype = i32
     l.mrirt_brats_sample_counts.argtypes = [C.POINTER(BratsParams), C.POINTER(RenderExt), vp, vp]
     l.mrirt_brats_emit_samples.argtypes = [C.POINTER(BratsParams), C.POINTER(RenderExt), C.POINTER(vp),
                                            C.POINTER(f32), C.POINTER(f32), vp, vp, vp, vp]

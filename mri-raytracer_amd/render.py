@@ -485,10 +485,24 @@ def _bind_order(P, E, vp, lab, prd, S, pitch, dev, stream):
     return O, t
 
 
+def _bind_tf(tf: ArrayLike, dev) -> torch.Tensor:
+    """A transfer-function table (transfer.py: (N, 4) rows of (r, g, b, sigma), 2 <= N <= 1024) as the contiguous, 16-byte
+    aligned fp32 device tensor ``mrirt_render_brats_tf`` reads.  A device tensor that already is one is bound as it is."""
+    t = tf if isinstance(tf, torch.Tensor) else torch.from_numpy(np.array(tf, dtype=np.float64))      # (a copy: the caller's array may be read-only)
+    if t.dim() != 2 or t.shape[1] != 4 or not t.is_floating_point():
+        raise ValueError(f"tf: expected an (N, 4) floating-point table of (r, g, b, sigma) rows, got {tuple(t.shape)} {t.dtype}")
+    if not 2 <= int(t.shape[0]) <= 1024:
+        raise ValueError(f"tf: a table has 2..1024 entries, got {int(t.shape[0])}")
+    t = t.to(device=dev, dtype=torch.float32).contiguous()
+    if t.data_ptr() % 16 != 0:
+        t = t.clone()                                   # (a view into another tensor: a fresh allocation is aligned)
+    return t
+
+
 def render_brats(params: Mapping[str, Any], intensities: Sequence[Optional[Union[ArrayLike, Grid]]],
                  labels: Optional[Union[ArrayLike, Grid]] = None, preds: Optional[Union[ArrayLike, Grid]] = None,
                  out: Optional[torch.Tensor] = None, ext: Optional[Mapping[str, Any]] = None,
-                 stats: bool = False, stream=None, skip: bool = False):
+                 stats: bool = False, stream=None, skip: bool = False, tf: Optional[ArrayLike] = None):
     """K1 — drop-in for ``kernel.dispatch`` of ``brats_main`` (inr/viewer/brats_viewer.py:431-442).
 
     ``params`` is the reference's ``gParams`` dict; ``intensities`` are ``gIntensity0..3``,
@@ -503,10 +517,32 @@ def render_brats(params: Mapping[str, Any], intensities: Sequence[Optional[Union
 
     ``ext["order"]`` (default ``ORDER_DEFAULT``): dispatch the launch's workgroups longest first by the step counts the
     previous frame on this stream recorded (``_bind_order``; same bits, same counters); ``False`` for A/B runs.
+
+    ``tf``: an RGBA transfer-function table (``transfer.py``: an ``(N, 4)`` array or device tensor of ``(r, g, b, sigma)`` rows,
+    2 <= N <= 1024) maps the windowed intensity to colour and extinction through ``mrirt_render_brats_tf``; ``None`` is the
+    grey ramp of the reference, the path above.  A table renders without skipping (``skip=True`` raises ``ValueError``) and
+    without a dispatch order (``ext["order"]`` is not used).
     """
     dev = _require_gpu()
     ext = dict(ext or {})
     ordered = bool(ext.pop("order", ORDER_DEFAULT))
+    if tf is not None:
+        if skip:
+            raise ValueError("render_brats: exact empty-space skipping is not defined under a transfer-function table (tf with skip=True)")
+        with _on_stream(stream):
+            P, E, vols, lab, prd, intensities = _bind_brats(params, intensities, labels, preds, ext, dev)
+            o, pitch = _alloc_out(int(P.imageSize[0]), int(P.imageSize[1]), E, dev, out)
+            vp = (C.c_void_p * 4)(*[C.c_void_p(t.data_ptr()) if t is not None else None for t in vols])
+            st = torch.zeros(2, dtype=torch.int64, device=dev) if stats else None
+            table = _bind_tf(tf, dev)
+            rc = _lib.lib().mrirt_render_brats_tf(C.byref(P), C.byref(E), vp, _ptr(lab), _ptr(prd), _ptr(table), int(table.shape[0]),
+                                                  _ptr(o), pitch, _ptr(st), _stream_ptr(stream))
+            _lib.check(rc, "mrirt_render_brats_tf")
+            if stats:
+                s = st.cpu()
+                return o, {"live_samples": int(s[0]), "shaded_samples": int(s[1])}
+            del table                                   # (only here: the launch that reads it has been enqueued)
+        return o
     # every temporary of this call (uploads of host arrays, the output, the counters, the skip mask) is made on
     # the launch stream, so the kernels are ordered after their producers and the caching allocator ties the
     # memory to that stream

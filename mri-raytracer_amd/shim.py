@@ -30,6 +30,9 @@ _ENTRY_POINTS = {
     "raymarch_cs": ("K3", {"render_texture", "gParams", "gEye", "gU", "gV", "gW"}),
     "compute_main": ("K4", {"gOutput", "gBVHNodes", "gTris", "gVerts", "gParams"}),
 }
+# globals a dispatch may bind or leave out.  gTransfer (build-defined, no counterpart in brats_rt.slang): an RGBA
+# transfer-function table of N x (r, g, b, sigma) floats, 2 <= N <= 1024 (transfer.py)
+_OPTIONAL_GLOBALS = {"brats_main": {"gTransfer"}}
 
 
 class Format(enum.Enum):
@@ -121,7 +124,7 @@ class ComputeKernel:
 
     def dispatch(self, thread_count: Sequence[int], vars: Mapping[str, Any],
                  command_encoder: Optional[CommandEncoder] = None, ext: Optional[Mapping[str, Any]] = None) -> None:
-        unknown = set(vars) - self._globals
+        unknown = set(vars) - self._globals - _OPTIONAL_GLOBALS.get(self.entry, set())
         if unknown:
             raise KeyError(f"{self.entry}: no such shader globals {sorted(unknown)}")
         missing = self._globals - set(vars)
@@ -220,7 +223,24 @@ class ComputeKernel:
         # exact empty-space skipping rides on the macro-cell summaries upload_grid attached to the cached grids
         skip = (self.device.skip_empty and vlay in ("vg", "vga", "quad", "mod4")
                 and all(b is None or (isinstance(b, _r.Grid) and (b.macro is not None or b.macros is not None)) for b in bound))
+        table = vars.get("gTransfer")
+        if table is not None:
+            # a bound table: the same grids through mrirt_render_brats_tf, which has no skipping
+            _r.render_brats(p, bound[:4], bound[4], bound[5], out=tex.tensor, ext=e, tf=self._transfer(table))
+            return
         _r.render_brats(p, bound[:4], bound[4], bound[5], out=tex.tensor, ext=e, skip=skip)
+
+    @staticmethod
+    def _transfer(table):
+        """gTransfer -> the (N, 4) table render_brats takes: a Buffer of N * 4 floats, or an array / tensor of that size."""
+        if isinstance(table, Buffer):
+            if table.tensor is None:
+                raise ValueError("gTransfer was never filled (copy_from_numpy)")
+            table = table.tensor
+        t = table if isinstance(table, torch.Tensor) else np.asarray(table)
+        if (not t.is_floating_point() if isinstance(t, torch.Tensor) else t.dtype.kind != "f") or len(t.reshape(-1)) % 4 != 0:
+            raise ValueError("gTransfer holds N x (r, g, b, sigma) floats")
+        return t.reshape(-1, 4)
 
     def _volume(self, tc, vars, ext):
         p, tex = vars["gParams"], vars["gOutput"]

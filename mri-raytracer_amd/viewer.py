@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from . import inr as inr_model
-from . import nifti, shim, volume
+from . import nifti, shim, transfer, volume
 from .camera import OrbitalCamera
 
 MOD_SUFFIXES = {"t1n": "T1n", "t1c": "T1c", "t2w": "T2w", "t2f": "FLAIR"}
@@ -51,7 +51,7 @@ def save_png(path, rgba: np.ndarray) -> None:
 
 class BraTSViewer:
     def __init__(self, case_dir: Optional[pathlib.Path] = None, up: str = "Y", layout: str = "auto", math_mode: str = "strict",
-                 prep: str = "host"):
+                 prep: str = "host", tf=None):
         self.device = shim.Device(enable_debug_layers=True, layout=layout, math=math_mode)
         program = self.device.load_program("brats_rt.slang", ["brats_main"])
         self.kernel = self.device.create_compute_kernel(program)
@@ -75,6 +75,8 @@ class BraTSViewer:
         self.seg_buffer = self.pred_buffer = None
         self._empty_float = self._create_buffer(np.zeros(1, dtype=np.float32))
         self._empty_uint = self._create_buffer(np.zeros(1, dtype=np.uint32))
+        self.transfer_buffer: Optional[shim.Buffer] = None      # gTransfer: None = the reference's grey ramp
+        self.set_transfer(tf)
         if case_dir is not None:
             self.load_dir(pathlib.Path(case_dir), prep=prep)
 
@@ -82,6 +84,18 @@ class BraTSViewer:
         b = self.device.create_buffer(element_count=linear.size, struct_size=4, usage=shim.BufferUsage.shader_resource)
         b.copy_from_numpy(linear)
         return b
+
+    def set_transfer(self, table_or_preset_name) -> None:
+        """The RGBA transfer-function table of the frames to come: an (N, 4) array of (r, g, b, sigma) rows (transfer.py), the name
+        of a preset ("gray", "hot": 256 entries), or None for the reference's grey ramp (the plain march)."""
+        if table_or_preset_name is None:
+            self.transfer_buffer = None
+            return
+        t = table_or_preset_name
+        table = transfer.tf_preset(t) if isinstance(t, str) else np.ascontiguousarray(np.asarray(t, dtype=np.float32))
+        if table.ndim != 2 or table.shape[1] != 4 or not transfer.TF_MIN_ENTRIES <= table.shape[0] <= transfer.TF_MAX_ENTRIES:
+            raise ValueError("a transfer-function table is (N, 4) with 2 <= N <= 1024")
+        self.transfer_buffer = self._create_buffer(table)
 
     # -- loading ---------------------------------------------------------------------------
     def _adopt_buffer(self, linear: torch.Tensor) -> shim.Buffer:
@@ -187,14 +201,14 @@ class BraTSViewer:
         if self.output_texture is None or (self.output_texture.width, self.output_texture.height) != (width, height):
             self.output_texture = self.device.create_texture(format=shim.Format.rgba16_float, width=width, height=height)
         ce = self.device.create_command_encoder()
-        self.kernel.dispatch(
-            thread_count=[width, height, 1],
-            vars={"gOutput": self.output_texture,
-                  "gIntensity0": self.buffers["T1n"], "gIntensity1": self.buffers["T1c"],
-                  "gIntensity2": self.buffers["T2w"], "gIntensity3": self.buffers["FLAIR"],
-                  "gLabels": self.seg_buffer or self._empty_uint, "gPreds": self.pred_buffer or self._empty_uint,
-                  "gParams": self.params(width, height)},
-            command_encoder=ce, ext=ext)
+        bound = {"gOutput": self.output_texture,
+                 "gIntensity0": self.buffers["T1n"], "gIntensity1": self.buffers["T1c"],
+                 "gIntensity2": self.buffers["T2w"], "gIntensity3": self.buffers["FLAIR"],
+                 "gLabels": self.seg_buffer or self._empty_uint, "gPreds": self.pred_buffer or self._empty_uint,
+                 "gParams": self.params(width, height)}
+        if self.transfer_buffer is not None:
+            bound["gTransfer"] = self.transfer_buffer
+        self.kernel.dispatch(thread_count=[width, height, 1], vars=bound, command_encoder=ce, ext=ext)
         self.device.submit_command_buffer(ce.finish())
         return self.output_texture
 
