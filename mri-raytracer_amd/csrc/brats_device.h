@@ -441,25 +441,42 @@ __device__ __forceinline__ const float4* stage_lut(const K1Args& a, float4* lutS
     return lutS;
 }
 
-template <bool STRICT, bool SHADE, bool GAMMA1 = false, bool LABELS = true>
+// What a sample's windowed intensity val does to the ray is composite()'s EVENT: sample() maps val to the emitted colour
+// e0..e2 and the extinction sigma, exp() is the exponential of the absorption step.  GreyRamp is the shader's own event
+// (:134-141): colour = extinction = val.  (The RGBA table's event: brats_tf.h.)
+// The policy interface, common to every event: `EventSample sample<STRICT>(val)`, `float exp<STRICT, LIT>(a, ex)` (an event may
+// ignore LIT and a), `kSeesZeroSign`.  Events travel by value: they are empty or two words, and a reference to a default
+// argument's temporary is one more stack object per call site, which moved the register allocation of kernels that only call
+// composite() with the default.
+struct EventSample { float e0, e1, e2, sigma; };
+struct GreyRamp {
+    static constexpr bool kSeesZeroSign = false;                     // no step after the blend can tell -0 from +0 (Stage::consume)
+    template <bool STRICT>
+    __device__ __forceinline__ EventSample sample(float val) const { return { val, val, val, val }; }
+    // constants: SGPR operands in the lean kernels; literals (LIT) where the shading / overlay state already fills
+    // the SGPR file (the 32 extra SGPRs spill there: measured +6 % on the 4-modality + overlay frame)
+    template <bool STRICT, bool LIT>
+    __device__ __forceinline__ float exp(const K1Args& a, float ex) const {
+        using Mm = M<STRICT>;
+        if (a.expSmall) return LIT ? Mm::exp_small_lit(ex) : Mm::exp_small(ex, a.ec);        // uniform: |ex| <= 1/8 for every sample
+        return LIT ? Mm::exp_lit(ex) : Mm::exp(ex, a.ec);
+    }
+};
+
+template <bool STRICT, bool SHADE, bool GAMMA1 = false, bool LABELS = true, class EVENT = GreyRamp>
 __device__ __forceinline__ void composite(const K1Args& a, const float rd[3], const Labels& lb, float v, const float g[3],
-                                          RayState& r, const float4* lutS = nullptr) {
+                                          RayState& r, const float4* lutS = nullptr, const EVENT ev = EVENT()) {
     using Mm = M<STRICT>;
     // wSum (brats_rt.slang:123-130) is the same for every sample: summed on the host
     if (a.wsum.d > 0.0f && a.wsum.d != 1.0f) v = Mm::divu_data(v, a.wsum);      // x / 1 == x: skip the three instructions
     float val = satf(Mm::divu_data(v - a.tfLo, a.wwDiv));                 // :132
     if constexpr (!GAMMA1) val = Mm::pow(val, a.gamma);              // :133
     ++r.nLive;
-    if (val > 0.0f) {
-        const float ex = -(val * a.intensityAlpha) * a.stepSize;
-        float e;
-        // constants: SGPR operands in the lean kernels; literals where the shading / overlay state already fills
-        // the SGPR file (the 32 extra SGPRs spill there: measured +6 % on the 4-modality + overlay frame)
-        constexpr bool LIT = SHADE || LABELS;
-        if (a.expSmall) e = LIT ? Mm::exp_small_lit(ex) : Mm::exp_small(ex, a.ec);        // uniform: |ex| <= 1/8 for every sample
-        else            e = LIT ? Mm::exp_lit(ex) : Mm::exp(ex, a.ec);
-        const float alpha = 1.0f - e;
-        float emis = val;
+    const EventSample s = ev.template sample<STRICT>(val);
+    if (s.sigma > 0.0f) {
+        const float ex = -(s.sigma * a.intensityAlpha) * a.stepSize;
+        const float alpha = 1.0f - ev.template exp<STRICT, SHADE || LABELS>(a, ex);
+        float e0 = s.e0, e1 = s.e1, e2 = s.e2;
         if constexpr (SHADE) {
             // headlight Blinn-Phong on the lattice gradient (build-defined extension):
             // world gradient = index-space difference * 0.5/voxelSize; n.l = |g.d| / |g|
@@ -474,11 +491,11 @@ __device__ __forceinline__ void composite(const K1Args& a, const float rd[3], co
                 for (uint32_t k = 0; k < a.specPow2; ++k) spec = spec * spec;
                 shade = (a.ka + a.kd * ndl) + a.ks * spec;
             }
-            emis = val * shade;
+            e0 *= shade; e1 *= shade; e2 *= shade;
             ++r.nShaded;
         }
-        const float c = (alpha * r.T) * emis;
-        r.C0 += c; r.C1 += c; r.C2 += c;
+        const float at = alpha * r.T;
+        r.C0 += at * e0; r.C1 += at * e1; r.C2 += at * e2;
         r.T *= (1.0f - alpha);
     }
     if (LABELS && a.showSeg != 0) {                                  // :143-151

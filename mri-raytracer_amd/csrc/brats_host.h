@@ -14,6 +14,14 @@ int prepare(const MrirtBratsParams* p, const MrirtRenderExt* ext, const void* co
             const void* labels, const void* preds, bool needVolumes, int64_t pitch_px,
             K1Args& a, Prepared& cfg);
 
+// One launch of a register-gather march kernel (brats_march.hip, brats_tf.hip): the grid and the workgroup size of prepare()'s
+// pixel map, `lds` bytes of dynamic shared memory.  args: the kernel's parameters, K1Args first.
+inline int launch_k1(const void* kernel, const K1Args& a, void** args, size_t lds, hipStream_t s) {
+    const dim3 grid(a.map.chunk * kXcds), block(a.map.blockPx == 8 ? 64 : 256);
+    MRIRT_HIP(hipLaunchKernel(kernel, grid, block, args, lds, s));
+    return MRIRT_OK;
+}
+
 // brats_skip.hip: the pre-pass of a skipping launch.  Builds the empty-radius map of `a`'s configuration in skip->mask
 // on `s` (unless skip->mapReady: the caller vouches that the scratch already holds it) and points a.skipDist / a.mX,
 // mXY, mY, mZ at it.

@@ -1,16 +1,20 @@
 // K1 with an RGBA transfer-function table: mrirt_render_brats_tf (include/mrirt.h).
 //
-// The march of brats_march.hip's generic kernel — ray set-up, sampleLinear's cell, the layouts' gathers (Taps), the label
-// fetches, the frame store and the counters are its code, shared through brats_device.h — with composite()'s grey ramp
-// replaced by a lookup in an N x (r, g, b, sigma) table (brats_tf.h: composite_tf).  The table sits in LDS: dynamic shared
-// memory of 16 N bytes per workgroup (N <= 1024: 16 KiB), filled once with coalesced 16-byte loads next to the overlay rows
-// of stage_lut, one barrier for both.
+// The march of brats_march.hip — ray set-up, sampleLinear's cell, the layouts' gathers (Taps), the label fetches, compositing
+// (composite(): window, level, gamma, shading, overlays), the frame store and the counters are its code, shared through
+// brats_device.h, and the pipeline's Stage is its Stage, shared through brats_stage.h — with composite()'s grey ramp replaced
+// by a lookup in an N x (r, g, b, sigma) table: TableEvent (brats_tf.h), the EVENT of composite() and of Stage.  The table sits
+// in LDS: dynamic shared memory of 16 N bytes per workgroup (N <= 1024: 16 KiB), filled once with coalesced 16-byte loads next
+// to the overlay rows of stage_lut, one barrier for both.
 //
-// Two kernel families: brats_tf_kernel<STRICT, LAYOUT, SHADE> — gathers issued and consumed per step, any subset of the four
-// modalities, 64-bit offsets: every layout — and brats_tf_pipe_kernel<STRICT, LAYOUT, CELLS>, the two-stage software pipeline
-// for the two viewer configurations (below; kernelVariant bit 2 keeps a launch on the generic kernel).  No skipping, no
-// dispatch order, no class stream.
+// What is this unit's own: stage_tf, the two kernels' loops, the choice of pipelined against generic, and the entry point's
+// checks.  Two kernel families: brats_tf_kernel<STRICT, LAYOUT, SHADE> — gathers issued and consumed per step, any subset of the
+// four modalities, 64-bit offsets: every layout — and brats_tf_pipe_kernel<STRICT, LAYOUT, CELLS>, the two-stage software pipeline
+// for the two viewer configurations (below; kernelVariant bit 2 keeps a launch on the generic kernel).  No skipping, no dispatch
+// order, no class stream.  (The loops are brats_march_kernel's and brats_march_pipe_kernel's, restated: as device functions
+// shared with those kernels they moved the code of most of them — DESIGN.md section 22.)
 #include "brats_host.h"
+#include "brats_stage.h"
 #include "brats_tf.h"
 
 namespace mrirt {
@@ -24,7 +28,7 @@ __global__ __launch_bounds__(256) void brats_tf_kernel(const K1Args a, const TfT
     __shared__ float4 lutShared[16];
     stage_tf(tf, tfShared);
     const float4* lutS = stage_lut(a, lutShared);                     // (its barrier covers the table too)
-    const float4* tfS = tfShared;
+    const TableEvent ev = { tf, tfShared };
     uint32_t px, py;
     int64_t oidx;
     const int kind = map_pixel(a.map, px, py, oidx);
@@ -41,7 +45,7 @@ __global__ __launch_bounds__(256) void brats_tf_kernel(const K1Args a, const TfT
             locate<STRICT>(a, ro, rd, t, s);
             float v = 0.0f, g[3] = { 0.0f, 0.0f, 0.0f };
             if constexpr (kMod4) {
-                // one tap set carries the four modalities (Stage, brats_march.hip): blended in ascending order, enabled ones only
+                // one tap set carries the four modalities (Stage, brats_stage.h): blended in ascending order, enabled ones only
                 Taps<2, true> taps;
                 float sv[4], rest[3];
                 taps.template issue<true>(a.vol[0], a.grid, s);
@@ -67,7 +71,7 @@ __global__ __launch_bounds__(256) void brats_tf_kernel(const K1Args a, const TfT
             }
             Labels lb;
             fetch_labels(a, s, lb);
-            composite_tf<STRICT, SHADE>(a, tf, tfS, rd, lb, v, g, r, lutS);
+            composite<STRICT, SHADE>(a, rd, lb, v, g, r, lutS, ev);
             t += a.stepSize;
         }
     }
@@ -75,80 +79,26 @@ __global__ __launch_bounds__(256) void brats_tf_kernel(const K1Args a, const TfT
 }
 
 // ---------------------------------------------------------------------------------------
-// Pipelined table kernels: the two-stage march of brats_march_pipe_kernel (same order: consume A(k); issue A(k+2);
-// consume B(k+1); issue B(k+3); one static issue site and one counted wait per stage, the pipeline filling inside the
-// loop) for exactly two configurations:
-//   MOD4, unshaded, overlays off (CELLS false) or through label cells (CELLS true): the viewer's frame, config C2;
-//   VGA, shaded, one modality, no overlays: config C3.
-// The gathers are Taps::issue_async's inline asm (brats_device.h: the compiler does not know they are loads), retired by
-// arrive<kLoads>; the table lookup of composite_tf sits between a stage's gathers and the other stage's wait and reads
-// LDS only, so it touches lgkmcnt and never vmcnt.  STRICT instances are compiled for gamma == 1 (no fp64 pow: registers);
-// any other STRICT gamma takes the generic kernel.  tests/test_tf_host.py runs tools/check_async_loads.py's in-flight scan
-// on these kernels (the build gate's own scan goes by the plain kernels' name).
+// Pipelined table kernels: the two-stage march of brats_march_pipe_kernel (same order, one static issue site and one counted
+// wait per stage, the pipeline filling inside the loop, the drain behind it: explained there) for exactly two configurations,
+// each an instance of the plain Stage:
+//   MOD4, unshaded, overlays off (CELLS false: 8 gathers) or through label cells (CELLS true: 9): the viewer's frame, config C2;
+//   VGA, shaded, one modality, no overlays (8 gathers): config C3.
+// TableEvent's lookup sits between a stage's gathers and the other stage's wait and reads LDS only, so it touches lgkmcnt and
+// never vmcnt.  STRICT instances are compiled for gamma == 1 (no fp64 pow: registers); any other STRICT gamma takes the generic
+// kernel.  tests/test_tf_host.py runs tools/check_async_loads.py's in-flight scan on these kernels (the build gate's own scan
+// goes by the plain kernels' name).
 // ---------------------------------------------------------------------------------------
-template <int LAYOUT, bool CELLS>
-struct TfStage {
-    static constexpr bool kMod4 = LAYOUT == MRIRT_LAYOUT_MOD4;
-    static_assert(kMod4 || (LAYOUT == MRIRT_LAYOUT_VGA && !CELLS), "MOD4 (with or without label cells) or VGA without overlays");
-    using TapSet = Taps<kMod4 ? 2 : 4, true>;
-    static constexpr int kLoads = 8 + (CELLS ? 1 : 0);               // vector-memory instructions issue_async() emits
-    Cell s;
-    TapSet taps;
-    u32x2 cw;                        // CELLS: the cell's two label words, in flight with the taps
-    uint32_t csh;                    // ... and which nibble of them is this sample's
-    __device__ __forceinline__ void issue_async(const K1Args& a, const WaveGrid<LAYOUT>& wg) {
-        CellOffsets k;
-        if constexpr (kMod4) k = vec4_cell(*wg.g, s.ix, s.iy, s.iz);
-        else k = flat_cell(wg.f, s.ix, s.iy, s.iz);
-        taps.issue_async(wg.base(a.vol[kMod4 ? 0u : a.chan[0]]), k);
-        if constexpr (CELLS) {
-            async_load_words2(cw, a.labCell, k.o << 3);
-            csh = label_corner_shift(a, s);
-        }
-    }
-    // every load of this stage has landed; YOUNGER = vector-memory instructions issued after them (the other stage's)
-    template <int YOUNGER>
-    __device__ __forceinline__ void arrive(const K1Args& a, Labels& lb) {
-        taps.template arrive<YOUNGER>();
-        if constexpr (CELLS) {
-            u32x2 w = cw;
-            asm volatile("" : "+v"(w));                                     // (the label words arrived with the taps: same wait)
-            labels_from_cell(a, w.x, w.y, csh, lb);
-        } else {
-            lb.seg = 0u; lb.pred = 0u;
-        }
-    }
-    template <bool STRICT>
-    __device__ __forceinline__ void consume(const K1Args& a, const TfTable& tf, const float4* tfS, const float rd[3], const Labels& lb,
-                                            RayState& r, const float4* lutS) const {
-        using Mm = M<STRICT>;
-        float v = 0.0f, g[3] = { 0.0f, 0.0f, 0.0f };
-        if constexpr (kMod4) {
-            float sv[4], rest[3];
-            taps.template eval<STRICT>(s, sv[0], rest);
-            sv[1] = rest[0]; sv[2] = rest[1]; sv[3] = rest[2];
-#pragma unroll
-            for (int m = 0; m < 4; ++m) if (a.enabled[m] != 0) v = Mm::mad(sv[m], a.weight[m], v);       // uniform branches
-            composite_tf<STRICT, false, STRICT>(a, tf, tfS, rd, lb, v, g, r, lutS);
-        } else {
-            float sv, gm[3];
-            taps.template eval<STRICT>(s, sv, gm);
-            const float w = a.weight[a.chan[0]];
-            v = Mm::mad(sv, w, v);                               // the generic kernel's arithmetic: 0 + s * w, likewise the gradient
-#pragma unroll
-            for (int k = 0; k < 3; ++k) g[k] = Mm::mad(gm[k], w, g[k]);
-            composite_tf<STRICT, true, STRICT>(a, tf, tfS, rd, lb, v, g, r, lutS);
-        }
-    }
-};
-
 template <bool STRICT, int LAYOUT, bool CELLS>
 __global__ __launch_bounds__(256, 3) void brats_tf_pipe_kernel(const K1Args a, const TfTable tf) {
+    constexpr bool kMod4 = LAYOUT == MRIRT_LAYOUT_MOD4;
+    static_assert(kMod4 || (LAYOUT == MRIRT_LAYOUT_VGA && !CELLS), "MOD4 (with or without label cells) or VGA without overlays");
+    using PipeStage = Stage<LAYOUT, !kMod4, kMod4 ? 4 : 1, CELLS, false, CELLS, TableEvent>;
     extern __shared__ float4 tfShared[];
     __shared__ float4 lutShared[16];
     stage_tf(tf, tfShared);
     const float4* lutS = stage_lut(a, lutShared);
-    const float4* tfS = tfShared;
+    const TableEvent ev = { tf, tfShared };
     uint32_t px, py;
     int64_t oidx;
     const int kind = map_pixel(a.map, px, py, oidx);
@@ -159,16 +109,15 @@ __global__ __launch_bounds__(256, 3) void brats_tf_pipe_kernel(const K1Args a, c
     if constexpr (LAYOUT == 4) wg.f = a.vga.ax[vga_pick_axis(a, ro, rd, marches)];      // every lane votes: outside the branch
     else wg.g = &a.grid;
     if (marches) {
-        TfStage<LAYOUT, CELLS> A, B;
-        constexpr int kN = TfStage<LAYOUT, CELLS>::kLoads;
-        Labels lb;
+        PipeStage A, B;
+        constexpr int kN = PipeStage::kLoads;
         float tI = t0;                                           // time of the next sample to ISSUE (the running sum)
         float tA = t0, tB = t0;                                  // time of the sample each stage holds
         uint32_t n = 0;
         while (true) {
             if (n != 0u) {
-                A.template arrive<kN>(a, lb);                    // B's kN loads may still be in flight
-                A.template consume<STRICT>(a, tf, tfS, rd, lb, r, lutS);
+                A.template arrive<kN>(a);                        // B's kN loads may still be in flight
+                A.template consume<STRICT, STRICT>(a, rd, r, lutS, ev);
                 if (!(tB < t1 && r.T > a.ert)) break;            // the loop test for the next sample (held by B)
             }
             tA = tI;
@@ -176,8 +125,8 @@ __global__ __launch_bounds__(256, 3) void brats_tf_pipe_kernel(const K1Args a, c
             A.issue_async(a, wg);
             tI += a.stepSize;
             if (n != 0u) {
-                B.template arrive<kN>(a, lb);
-                B.template consume<STRICT>(a, tf, tfS, rd, lb, r, lutS);
+                B.template arrive<kN>(a);
+                B.template consume<STRICT, STRICT>(a, rd, r, lutS, ev);
                 if (!(tA < t1 && r.T > a.ert)) break;
             }
             tB = tI;
@@ -252,9 +201,6 @@ extern "C" int mrirt_render_brats_tf(const MrirtBratsParams* p, const MrirtRende
     tf.n = tf_entries;
     tf.last = tf_entries - 2u;
     tf.top = (float)(tf_entries - 1u);
-    const dim3 grid(a.map.chunk * kXcds), block(a.map.blockPx == 8 ? 64 : 256);
     void* args[] = { &a, &tf };
-    MRIRT_HIP(hipLaunchKernel(reinterpret_cast<const void*>(k), grid, block, args, (size_t)tf_entries * sizeof(float4),
-                              static_cast<hipStream_t>(stream)));
-    return MRIRT_OK;
+    return launch_k1(reinterpret_cast<const void*>(k), a, args, (size_t)tf_entries * sizeof(float4), static_cast<hipStream_t>(stream));
 }
