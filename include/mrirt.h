@@ -48,7 +48,10 @@ extern "C" {
  *    case preparation (no new struct): mrirt_prep_scratch_bytes, mrirt_prep_window, mrirt_prep_normalize,
  *    mrirt_prep_zscore_scratch_bytes, mrirt_prep_zscore_stats, mrirt_prep_zscore_apply, mrirt_prep_gaussian3d;
  *    connected components (no new struct): mrirt_cc_scratch_bytes, mrirt_cc_label, mrirt_cc_sizes, mrirt_cc_filter,
- *    mrirt_slice_counts. */
+ *    mrirt_slice_counts;
+ *    the coordinate-injection INR: MrirtInjectDesc, MrirtInjectDropout (mrirt_sizeof(17), (18)), mrirt_inject_scratch_bytes,
+ *    mrirt_inject_forward, mrirt_inject_uncertainty, mrirt_inject_predict_volume, mrirt_boundary_weights_scratch_bytes,
+ *    mrirt_boundary_weights. */
 #define MRIRT_ABI_VERSION 4
 
 typedef enum MrirtStatus {
@@ -994,6 +997,81 @@ int mrirt_prep_gaussian3d(const float* vol, const uint32_t dims[3], const double
                           float* scratch, void* stream);
 
 /* ------------------------------------------------------------------------------------ */
+/* Coordinate-injection INR: forward, volume prediction, MC-dropout entropy, boundary map */
+/* ------------------------------------------------------------------------------------ */
+/* Added within ABI 4: new symbols and two new structs only, mrirt_sizeof(17) and (18)   */
+/* The third network of the reference (notebooks/improved.ipynb, cells 6 - 10): a learnable Gaussian Fourier projection B, an
+ * MLP that takes the coordinates and the modalities again in its hidden layers, dropout after every hidden ReLU.  fp32, every
+ * operation separate (the library is built with -ffp-contract=off).  DESIGN.md section 23.
+ *
+ * Network: L = numLayers linear layers, the head included, 2 <= L <= 8.  Fourier width F = fourierDim, even, 2 <= F <= 256; B is
+ * [F / 2][3] fp32, row-major.  M = numMods <= 8.  width[l] (1 <= width[l] <= 256) is layer l's output width; C = width[L - 1]
+ * <= 16 classes.  Bit l of coordLayers / modLayers may be set only for 1 <= l <= L - 2 (the head takes h alone).  Input widths:
+ *   in_0 = F + M;   in_l = width[l - 1] + 3 [l in coordLayers] + M [l in modLayers]  (1 <= l <= L - 2);   in_{L-1} = width[L - 2]
+ * with the concatenation order [h, coords, mods].  w: fp32 [in][out] per layer, the layers one after the other, unpadded; b
+ * likewise (the layout of the other fp32 entry points).
+ * Features of a point with coordinates c (fp32, unfused, in this order):
+ *   c01_a = (c_a + 1.0f) * 0.5f;   p_j = ((c01_x B[j][0]) + (c01_y B[j][1])) + (c01_z B[j][2]);   a_j = 6.2831855f * p_j
+ *   (s_j, k_j) = the STRICT sine and cosine of a_j (csrc/siren_sincos.h: float32(sin(double(a))); |a| > 2^20 gives +0 and 1, NaN
+ *   and +-inf give NaN);   x0 = [s_0 .. s_{F/2-1}, k_0 .. k_{F/2-1}, mods]
+ * Layers: z = x W + b on v_mfma_f32_16x16x4_f32 (products summed in increasing k, the bias added once after the sum), below the
+ * head h = max(z, 0) as jnp.maximum has it (-0 gives +0, a NaN stays).  argmax: the first index of the maximum, a NaN counting as
+ * the maximum (np.argmax).
+ * Dropout (the library's own rule, not JAX's key stream): keep in (0, 1]; keep == 1 masks nothing.  Element (point i, layer
+ * l <= L - 2, unit j) of sample s draws Philox4x32-10 under key (seed lo, seed hi) at counter (i lo, i hi, 256 s + l, j >> 2) and
+ * takes word j & 3: kept iff word < floor((double)keep 2^32).  A kept value is multiplied by scale = 1.0f / keep (computed once on
+ * the host), a dropped one is +0.  i is the GLOBAL point index: index0 + the row for the point entry points, the C-order voxel
+ * index (x W + y) D + z for a volume, so neither chunking nor splitting a call changes a mask.
+ * Uncertainty: p_s = softmax(logits_s) (subtract the maximum, expf, one division by the sum as a reciprocal multiply);
+ *   mean_k = (sum_s p_s[k], s ascending, fp32) / (float)S;   entropy = -(sum_k mean_k * logf(mean_k + 1e-10f)), k ascending. */
+typedef struct MrirtInjectDesc {
+    uint32_t numLayers, fourierDim, numMods;
+    uint32_t width[8];
+    uint32_t coordLayers, modLayers;
+} MrirtInjectDesc;
+typedef struct MrirtInjectDropout {
+    uint64_t seed;
+    float keep;
+    uint32_t samples;          /* S, 1..64; mrirt_inject_forward takes 1 only                                               */
+    uint32_t sample0;          /* the first sample's index s (the others follow); sample0 + samples <= 2^24                  */
+    uint32_t reserved;         /* 0                                                                                          */
+    uint64_t index0;           /* global index of row 0 of a point entry point; 0 for a volume                               */
+} MrirtInjectDropout;
+/* Every pointer but desc / dropout / hwd is a device pointer; the work is a chain of launches on `stream`, nothing
+ * synchronises with the host, nothing is allocated, there are no float atomics and every element has one writer: the same
+ * inputs give the same bits.  scratch: 16-byte aligned, at least mrirt_inject_scratch_bytes(desc, n) bytes (n = chunk for a
+ * volume); that size is monotone in n and 0 for a refused desc or n outside 1 .. 2^31 - 1.
+ * Checked before anything is launched: MRIRT_ERR_NULL for a NULL desc, B, w, b, coords, mods (unless numMods == 0), hwd,
+ * scratch or required output; MRIRT_ERR_ARG for a bad shape or injection bit, n / chunk outside 1 .. 2^31 - 1, keep outside
+ * (0, 1], samples outside 1..64 (forward: other than 1), sample0 + samples > 2^24, reserved != 0, an axis < 2 or H W D >= 2^31,
+ * a misaligned or too-small scratch.
+ * forward: coords [n][3], mods [n][M]; logits [n][C] and / or argmax [n] (int16), either may be NULL but not both; dropout NULL
+ *   is the evaluation forward.
+ * uncertainty: S = dropout->samples passes s = sample0 .. sample0 + S - 1 -> entropy [n]; mean_probs [n][C] may be NULL.
+ * predict_volume: mods [M][H][W][D] fp32 C order, the coordinate of index i on an axis of extent E is
+ *   ((float)i / (float)(E - 1)) * 2.0f - 1.0f; pred [H][W][D] int16 from the evaluation forward; entropy [H][W][D] fp32 (may be
+ *   NULL; then dropout must be NULL too, and with entropy dropout is required); `chunk` points per pass.  The result does not
+ *   depend on chunk. */
+int64_t mrirt_inject_scratch_bytes(const MrirtInjectDesc* desc, int64_t n);
+int mrirt_inject_forward(const MrirtInjectDesc* desc, const float* B, const float* w, const float* b, const float* coords,
+                         const float* mods, int64_t n, const MrirtInjectDropout* dropout, float* logits, int16_t* argmax,
+                         void* scratch, int64_t scratch_bytes, void* stream);
+int mrirt_inject_uncertainty(const MrirtInjectDesc* desc, const float* B, const float* w, const float* b, const float* coords,
+                             const float* mods, int64_t n, const MrirtInjectDropout* dropout, float* entropy, float* mean_probs,
+                             void* scratch, int64_t scratch_bytes, void* stream);
+int mrirt_inject_predict_volume(const MrirtInjectDesc* desc, const float* B, const float* w, const float* b, const float* mods,
+                                const uint32_t hwd[3], int64_t chunk, const MrirtInjectDropout* dropout, int16_t* pred,
+                                float* entropy, void* scratch, int64_t scratch_bytes, void* stream);
+/* The boundary weight map of the notebook's cache (cell 5): out[v] = float32(max over c = 1 .. num_classes - 1 of
+ * 1.0 / (1.0 + sqrt(d2_c[v]))) in fp64, d2_c the exact squared distance (unit spacing) to the nearest voxel of class c
+ * (mrirt_edt_squared); a class that does not occur contributes 0, so the map is 0 where no tumour class is present.
+ * labels: int16 [H][W][D]; every axis 1..4096, H W D < 2^31, num_classes 1..32 (else MRIRT_ERR_ARG).  scratch: 16-byte aligned,
+ * mrirt_boundary_weights_scratch_bytes(hwd) bytes (one fp64 field; 0 for a refused volume). */
+int64_t mrirt_boundary_weights_scratch_bytes(const uint32_t hwd[3]);
+int mrirt_boundary_weights(const int16_t* labels, const uint32_t hwd[3], uint32_t num_classes, float* out, void* scratch,
+                           int64_t scratch_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------ */
 /* Misc                                                                                  */
 /* ------------------------------------------------------------------------------------ */
 int mrirt_abi_version(void);
@@ -1001,8 +1079,9 @@ const char* mrirt_status_string(int status);
 int mrirt_last_hip_error(void);            /* hipError_t of the last failed HIP call on this thread */
 uint32_t mrirt_sizeof(uint32_t which);     /* 0 BratsParams, 1 RenderExt, 2 VolumeParams, 3 SdfParams, 4 InrDesc, 5 Skip,
                                               6 MeshParams, 7 InrCache, 8 AdamW, 9 InrTrainCfg, 10 InrTrainState,
-                                              11 Muon, 13 InrLossExt, 14 InrTumourIndex, 15 InrTrainExt; 12 is
-                                              unassigned and stays 0, as every index beyond 15 */
+                                              11 Muon, 13 InrLossExt, 14 InrTumourIndex, 15 InrTrainExt, 17 InjectDesc,
+                                              18 InjectDropout; 12 and 16 are unassigned and stay 0, as every index
+                                              beyond 18 */
 /* Opt-in diagnostics (host only; the library installs nothing by itself): a SIGABRT handler that writes the native
  * backtrace of the aborting thread and, when file descriptor 2 has been redirected into a regular file (a test runner's
  * capture), the tail of that file to `fd` — a descriptor the caller duplicated before the redirection — and then chains

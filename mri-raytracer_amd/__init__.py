@@ -24,6 +24,8 @@ from .camera import OrbitalCamera  # noqa: F401
 from .components import component_sizes, label_components, remove_small_components, slice_counts  # noqa: F401
 from .grad import render_brats_autograd, render_brats_backward  # noqa: F401
 from .inr import apply_mlp, build_input, compute_multi_metrics, inr_forward, model_load, predict_volume, prepare_case, render_brats_inr  # noqa: F401
+from .inr import (boundary_weights, compute_uncertainty_mc_dropout, inject_desc, inject_dropout, inject_forward, inject_load,  # noqa: F401
+                  predict_full_volume)
 from .mesh import (build_bvh, extract_surface, load_ply, normalize_mesh, render_mesh, surface_mesh,  # noqa: F401
                    upload_mesh)
 from .shim import Device, KernelShim  # noqa: F401

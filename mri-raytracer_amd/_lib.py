@@ -17,7 +17,7 @@ CSRC = PKG_DIR / "csrc"
 INCLUDE = PKG_DIR.parent / "include"
 SO_PATH = pathlib.Path(os.environ.get("MRIRT_LIB", PKG_DIR / "libmrirt.so"))   # override: A/B builds in development
 HIP_SOURCES = ["brats_march.hip", "brats_order.hip", "brats_skip.hip", "brats_c5.hip", "brats_slab.hip", "brats_ring.hip", "brats_backward.hip", "brats_soft.hip", "brats_tf.hip", "volume_march.hip", "grid_ops.hip", "inr_mlp.hip",
-               "inr_stream.hip", "inr_ws.hip", "inr_refine.hip", "inr_train.hip", "inr_optim.hip", "inr_muon.hip", "inr_lossx.hip", "mesh_rt.hip", "edt.hip", "surface.hip", "prep.hip", "components.hip", "abort_trace.cpp"]
+               "inr_stream.hip", "inr_ws.hip", "inr_refine.hip", "inr_train.hip", "inr_optim.hip", "inr_muon.hip", "inr_lossx.hip", "inr_inject.hip", "mesh_rt.hip", "edt.hip", "surface.hip", "prep.hip", "components.hip", "abort_trace.cpp"]
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17", "-Wall"]
 
 # every extern "C" symbol include/mrirt.h declares
@@ -46,6 +46,8 @@ ABI_SYMBOLS = [
     "mrirt_prep_zscore_stats", "mrirt_prep_zscore_apply", "mrirt_prep_gaussian3d",
     "mrirt_cc_scratch_bytes", "mrirt_cc_label", "mrirt_cc_sizes", "mrirt_cc_filter", "mrirt_slice_counts",
     "mrirt_render_brats_tf",
+    "mrirt_inject_scratch_bytes", "mrirt_inject_forward", "mrirt_inject_uncertainty", "mrirt_inject_predict_volume",
+    "mrirt_boundary_weights_scratch_bytes", "mrirt_boundary_weights",
 ]
 
 ABI_VERSION = 4          # MRIRT_ABI_VERSION of include/mrirt.h this binding was written against
@@ -169,6 +171,16 @@ class InrTumourIndex(C.Structure):
 class InrTrainExt(C.Structure):
     """MrirtInrTrainExt: what mrirt_inr_train_run_ext takes beyond the plain run; every member may be NULL / 0."""
     _fields_ = [("loss", C.POINTER(InrLossExt)), ("muon", C.POINTER(Muon)), ("tumour", InrTumourIndex), ("nTumour", C.c_int64)]
+
+
+class InjectDesc(C.Structure):
+    """MrirtInjectDesc: the coordinate-injection network of notebooks/improved.ipynb."""
+    _fields_ = [("numLayers", u32), ("fourierDim", u32), ("numMods", u32), ("width", u32 * 8), ("coordLayers", u32), ("modLayers", u32)]
+
+
+class InjectDropout(C.Structure):
+    """MrirtInjectDropout: the Philox mask stream of one call."""
+    _fields_ = [("seed", C.c_uint64), ("keep", f32), ("samples", u32), ("sample0", u32), ("reserved", u32), ("index0", C.c_uint64)]
 
 
 class Skip(C.Structure):
@@ -480,6 +492,19 @@ def lib() -> C.CDLL:
     l.mrirt_cc_filter.restype = i32
     l.mrirt_slice_counts.argtypes = [vp, C.POINTER(u32), vp, vp]
     l.mrirt_slice_counts.restype = i32
+    inj = [C.POINTER(InjectDesc), vp, vp, vp]
+    l.mrirt_inject_scratch_bytes.argtypes = [C.POINTER(InjectDesc), i64]
+    l.mrirt_inject_scratch_bytes.restype = i64
+    l.mrirt_inject_forward.argtypes = [*inj, vp, vp, i64, C.POINTER(InjectDropout), vp, vp, vp, i64, vp]
+    l.mrirt_inject_forward.restype = i32
+    l.mrirt_inject_uncertainty.argtypes = [*inj, vp, vp, i64, C.POINTER(InjectDropout), vp, vp, vp, i64, vp]
+    l.mrirt_inject_uncertainty.restype = i32
+    l.mrirt_inject_predict_volume.argtypes = [*inj, vp, C.POINTER(u32), i64, C.POINTER(InjectDropout), vp, vp, vp, i64, vp]
+    l.mrirt_inject_predict_volume.restype = i32
+    l.mrirt_boundary_weights_scratch_bytes.argtypes = [C.POINTER(u32)]
+    l.mrirt_boundary_weights_scratch_bytes.restype = i64
+    l.mrirt_boundary_weights.argtypes = [vp, C.POINTER(u32), u32, vp, vp, i64, vp]
+    l.mrirt_boundary_weights.restype = i32
     l.mrirt_status_string.argtypes = [i32]
     l.mrirt_status_string.restype = C.c_char_p
     l.mrirt_sizeof.argtypes = [u32]
@@ -495,6 +520,9 @@ def lib() -> C.CDLL:
     for which, st in enumerate((BratsParams, RenderExt, VolumeParams, SdfParams, InrDesc, Skip, MeshParams, InrCache, AdamW, InrTrainCfg,
                                 InrTrainState, Muon, None, InrLossExt, InrTumourIndex, InrTrainExt)):          # index 12 is unassigned
         if st is not None and l.mrirt_sizeof(which) != C.sizeof(st):
+            raise ImportError(f"ABI mismatch: {st.__name__} is {C.sizeof(st)} B here, {l.mrirt_sizeof(which)} B in {SO_PATH}")
+    for which, st in ((17, InjectDesc), (18, InjectDropout)):                                              # 16 is unassigned
+        if l.mrirt_sizeof(which) != C.sizeof(st):
             raise ImportError(f"ABI mismatch: {st.__name__} is {C.sizeof(st)} B here, {l.mrirt_sizeof(which)} B in {SO_PATH}")
     _LIB = l
     return l

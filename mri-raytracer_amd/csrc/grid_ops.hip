@@ -454,6 +454,8 @@ extern "C" uint32_t mrirt_sizeof(uint32_t which) {
         case 13: return (uint32_t)sizeof(MrirtInrLossExt);          // 12 stays unassigned (0): it was, and callers may rely on it
         case 14: return (uint32_t)sizeof(MrirtInrTumourIndex);
         case 15: return (uint32_t)sizeof(MrirtInrTrainExt);
+        case 17: return (uint32_t)sizeof(MrirtInjectDesc);          // 16 stays unassigned too
+        case 18: return (uint32_t)sizeof(MrirtInjectDropout);
         default: return 0;
     }
 }

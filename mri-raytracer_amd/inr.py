@@ -14,6 +14,8 @@ model_load, predict_volume``: inr/interactive.ipynb cell 5, inr/viewer/brats_vie
   VoxelCache(cases).sample(seed, batch_index, n) / .sample_voxels(...)  dataloader.py:86-96,133-155
   siren_init / make_siren_loss_and_grad / siren_autograd / train_siren   neumors_inr.ipynb:1150-1200 (csrc/inr_train.hip)
   render_brats_inr_autograd / fit_views                                 docs/Goals.md "gradients flow: pixels -> raytracer -> MLP weights" (csrc/brats_soft.hip)
+  inject_load / inject_forward / predict_full_volume /                  notebooks/improved.ipynb cells 5 - 10, 14 (csrc/inr_inject.hip)
+  compute_uncertainty_mc_dropout / boundary_weights
 
 ``params`` is the reference's list of ``{"W": [in,out], "b": [out]}`` (SIREN: dict ``l{i}`` ->
 ``{"w","b"}``).  All arithmetic runs in the kernels behind csrc/inr_mlp.hip
@@ -1391,3 +1393,157 @@ def fit_views(config: Dict[str, Any], views: Sequence[Dict[str, Any]], targets: 
         if log is not None:
             log(step, losses[-1])
     return losses, st
+
+
+# ---- the coordinate-injection INR of notebooks/improved.ipynb (csrc/inr_inject.hip) -----------------------
+
+def inject_load(npz) -> Dict[str, Any]:
+    """The notebook's flat checkpoint (cell 14: ``fourier_B``, ``mlp_W_i``, ``mlp_b_i``) as the nested ``params`` it trains:
+    ``{"fourier": {"B"}, "mlp": [{"W", "b"}, ...]}``, fp32; the widths are the arrays' shapes.  ``npz``: a path or an open
+    ``np.load`` mapping."""
+    z = np.load(npz) if isinstance(npz, (str, pathlib.Path)) else npz
+    if "fourier_B" not in z:
+        raise KeyError("inject_load: no fourier_B in the checkpoint")
+    mlp = []
+    while f"mlp_W_{len(mlp)}" in z:
+        i = len(mlp)
+        mlp.append({"W": np.asarray(z[f"mlp_W_{i}"], np.float32), "b": np.asarray(z[f"mlp_b_{i}"], np.float32)})
+    if len(mlp) < 2:
+        raise ValueError("inject_load: expected at least two layers (mlp_W_0, mlp_W_1)")
+    return {"fourier": {"B": np.asarray(z["fourier_B"], np.float32)}, "mlp": mlp}
+
+
+def _inject_np(t) -> np.ndarray:
+    return (t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)).astype(np.float32)
+
+
+def inject_desc(params, coord_layers=(1, 2, 3), mod_layers=(2,)) -> _lib.InjectDesc:
+    """MrirtInjectDesc of ``params``.  Layer indices the notebook's loop never reaches (0, and L - 1 on: its own
+    ``COORD_INJECTION_LAYERS = [1, 2, 3]`` names one) are dropped here; the C ABI refuses them.  The number of modalities is
+    what layer 0's input holds beyond the Fourier features, and every other input width must follow from the two sets."""
+    B = _inject_np(params["fourier"]["B"])
+    Ws = [_inject_np(p["W"]) for p in params["mlp"]]
+    L, F = len(Ws), 2 * B.shape[0]
+    if B.ndim != 2 or B.shape[1] != 3 or not 2 <= L <= 8:
+        raise ValueError(f"inject_desc: B {B.shape} with {L} layers is not a coordinate-injection net")
+    M = Ws[0].shape[0] - F
+    d = _lib.InjectDesc()
+    d.numLayers, d.fourierDim, d.numMods = L, F, max(M, 0)
+    for l, W in enumerate(Ws):
+        d.width[l] = W.shape[1]
+    d.coordLayers = sum(1 << l for l in set(int(v) for v in coord_layers) if 0 < l < L - 1)
+    d.modLayers = sum(1 << l for l in set(int(v) for v in mod_layers) if 0 < l < L - 1)
+    for l, W in enumerate(Ws):
+        prev = F if l == 0 else Ws[l - 1].shape[1]
+        want = prev + (M if l == 0 else 3 * ((d.coordLayers >> l) & 1) + M * ((d.modLayers >> l) & 1))
+        if M < 0 or W.shape[0] != want or np.shape(params["mlp"][l]["b"]) != (W.shape[1],):
+            raise ValueError(f"inject_desc: layer {l} has a {W.shape} weight, the injection sets give {want} inputs")
+    return d
+
+
+def _inject_flat(params, dev):
+    w = np.concatenate([_inject_np(p["W"]).reshape(-1) for p in params["mlp"]])
+    b = np.concatenate([_inject_np(p["b"]).reshape(-1) for p in params["mlp"]])
+    return _dev_f32(_inject_np(params["fourier"]["B"]), dev), _dev_f32(w, dev), _dev_f32(b, dev)
+
+
+def inject_dropout(seed: int = 0, keep: float = 0.7, samples: int = 1, sample0: int = 0, index0: int = 0) -> _lib.InjectDropout:
+    d = _lib.InjectDropout()
+    d.seed, d.keep, d.samples, d.sample0, d.reserved, d.index0 = int(seed) & (2 ** 64 - 1), float(keep), int(samples), int(sample0), 0, int(index0)
+    return d
+
+
+def _inject_scratch(desc: _lib.InjectDesc, n: int, dev):
+    nbytes = int(_lib.lib().mrirt_inject_scratch_bytes(C.byref(desc), int(n)))
+    if nbytes <= 0:
+        raise _lib.MrirtError(-5, "mrirt_inject_scratch_bytes")
+    return torch.empty(nbytes // 8, dtype=torch.int64, device=dev), nbytes
+
+
+def _inject_points(coords, mods, dev, M: int):
+    c = _dev_f32(coords, dev).reshape(-1, 3)
+    m = _dev_f32(mods, dev).reshape(c.shape[0], M) if M else None
+    return c, m
+
+
+def inject_forward(params, coords, mods, *, dropout: Optional[_lib.InjectDropout] = None, coord_layers=(1, 2, 3), mod_layers=(2,),
+                   want_argmax: bool = False):
+    """Logits (n, C) fp32 of the notebook's ``apply_coord_injection_mlp(apply_fourier_features(...))`` at ``coords`` (n, 3),
+    ``mods`` (n, M); with ``want_argmax`` also the int16 class per point.  ``dropout=None`` is ``training=False``; an
+    ``inject_dropout(seed, keep, sample0=s, index0=i0)`` draws sample ``s`` of the library's mask stream."""
+    dev = _require_gpu()
+    desc = inject_desc(params, coord_layers, mod_layers)
+    c, m = _inject_points(coords, mods, dev, desc.numMods)
+    n = c.shape[0]
+    B, w, b = _inject_flat(params, dev)
+    logits = torch.empty((n, desc.width[desc.numLayers - 1]), dtype=torch.float32, device=dev)
+    am = torch.empty(n, dtype=torch.int16, device=dev) if want_argmax else None
+    scratch, nbytes = _inject_scratch(desc, n, dev)
+    rc = _lib.lib().mrirt_inject_forward(C.byref(desc), _ptr(B), _ptr(w), _ptr(b), _ptr(c), _ptr(m) if m is not None else None, n,
+                                         C.byref(dropout) if dropout is not None else None, _ptr(logits),
+                                         _ptr(am) if am is not None else None, _ptr(scratch), nbytes, _stream_ptr(None))
+    _lib.check(rc, "mrirt_inject_forward")
+    return (logits, am) if want_argmax else logits
+
+
+def compute_uncertainty_mc_dropout(params, coords, mods, n_samples: int = 5, seed: int = 0, dropout_rate: float = 0.3, *,
+                                   coord_layers=(1, 2, 3), mod_layers=(2,), want_mean: bool = False, index0: int = 0):
+    """The notebook's MC-dropout uncertainty (cell 9): the entropy (n,) fp32 of the mean softmax of ``n_samples`` dropout
+    passes, under the library's Philox mask stream keyed by ``seed`` (not JAX's key stream).  ``want_mean``: also the mean
+    probabilities (n, C)."""
+    dev = _require_gpu()
+    desc = inject_desc(params, coord_layers, mod_layers)
+    c, m = _inject_points(coords, mods, dev, desc.numMods)
+    n = c.shape[0]
+    B, w, b = _inject_flat(params, dev)
+    dp = inject_dropout(seed, float(np.float32(1.0) - np.float32(dropout_rate)), n_samples, 0, index0)
+    ent = torch.empty(n, dtype=torch.float32, device=dev)
+    mean = torch.empty((n, desc.width[desc.numLayers - 1]), dtype=torch.float32, device=dev) if want_mean else None
+    scratch, nbytes = _inject_scratch(desc, n, dev)
+    rc = _lib.lib().mrirt_inject_uncertainty(C.byref(desc), _ptr(B), _ptr(w), _ptr(b), _ptr(c), _ptr(m) if m is not None else None, n,
+                                             C.byref(dp), _ptr(ent), _ptr(mean) if mean is not None else None, _ptr(scratch), nbytes,
+                                             _stream_ptr(None))
+    _lib.check(rc, "mrirt_inject_uncertainty")
+    return (ent, mean) if want_mean else ent
+
+
+def predict_full_volume(params, case_data: Dict[str, Any], chunk_size: int = 50000, *, uncertainty: Optional[_lib.InjectDropout] = None,
+                        coord_layers=(1, 2, 3), mod_layers=(2,)):
+    """The notebook's ``predict_full_volume`` (cell 10): ``(pred int16 (H, W, D), case_data["seg"])`` for ``case_data["mods"]``
+    (M, H, W, D), ``chunk_size`` voxels per pass (the result does not depend on it).  ``uncertainty=inject_dropout(seed, keep,
+    samples=S)`` adds the MC-dropout entropy volume (H, W, D) fp32 as a third value: an ordinary scalar grid, which
+    ``volume.upload_grid`` and ``render_brats(tf=tf_preset("hot"))`` draw as they draw a modality."""
+    dev = _require_gpu()
+    desc = inject_desc(params, coord_layers, mod_layers)
+    mods = _dev_f32(case_data["mods"], dev)
+    if mods.dim() != 4 or mods.shape[0] != desc.numMods:
+        raise ValueError(f"predict_full_volume: mods {tuple(mods.shape)} for a net of {desc.numMods} modalities")
+    _, H, W, D = mods.shape
+    chunk = max(1, min(int(chunk_size), H * W * D))
+    B, w, b = _inject_flat(params, dev)
+    pred = torch.empty((H, W, D), dtype=torch.int16, device=dev)
+    ent = torch.empty((H, W, D), dtype=torch.float32, device=dev) if uncertainty is not None else None
+    scratch, nbytes = _inject_scratch(desc, chunk, dev)
+    hwd = (C.c_uint32 * 3)(H, W, D)
+    rc = _lib.lib().mrirt_inject_predict_volume(C.byref(desc), _ptr(B), _ptr(w), _ptr(b), _ptr(mods) if desc.numMods else None, hwd, chunk,
+                                                C.byref(uncertainty) if uncertainty is not None else None, _ptr(pred),
+                                                _ptr(ent) if ent is not None else None, _ptr(scratch), nbytes, _stream_ptr(None))
+    _lib.check(rc, "mrirt_inject_predict_volume")
+    return (pred, case_data["seg"], ent) if ent is not None else (pred, case_data["seg"])
+
+
+def boundary_weights(seg, num_classes: int = 4) -> torch.Tensor:
+    """The boundary weight map of the notebook's cache (cell 5): ``max_c 1 / (1 + edt(seg != c))`` over the tumour classes
+    c = 1 .. num_classes - 1 that occur, fp32 (H, W, D) on the device, 0 where none does; bit for bit SciPy's
+    ``distance_transform_edt`` loop, from the exact fp64 distance transform of csrc/edt.hip."""
+    dev = seg.device if isinstance(seg, torch.Tensor) and seg.is_cuda else _require_gpu()
+    lab = _label_volume(seg, dev, "seg")
+    hwd = (C.c_uint32 * 3)(*lab.shape)
+    lib = _lib.lib()
+    with torch.cuda.device(dev):
+        nbytes = int(lib.mrirt_boundary_weights_scratch_bytes(hwd))
+        out = torch.empty(tuple(lab.shape), dtype=torch.float32, device=dev)
+        scratch = torch.empty(max(nbytes, 8) // 8, dtype=torch.int64, device=dev)
+        rc = lib.mrirt_boundary_weights(_ptr(lab), hwd, int(num_classes), _ptr(out), _ptr(scratch), nbytes, _stream_ptr(None))
+    _lib.check(rc, "mrirt_boundary_weights")
+    return out
