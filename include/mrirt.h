@@ -51,7 +51,8 @@ extern "C" {
  *    mrirt_slice_counts;
  *    the coordinate-injection INR: MrirtInjectDesc, MrirtInjectDropout (mrirt_sizeof(17), (18)), mrirt_inject_scratch_bytes,
  *    mrirt_inject_forward, mrirt_inject_uncertainty, mrirt_inject_predict_volume, mrirt_boundary_weights_scratch_bytes,
- *    mrirt_boundary_weights. */
+ *    mrirt_boundary_weights;
+ *    its training step (no new struct): mrirt_inject_train_scratch_bytes, mrirt_inject_forward_train, mrirt_inject_backward. */
 #define MRIRT_ABI_VERSION 4
 
 typedef enum MrirtStatus {
@@ -1070,6 +1071,48 @@ int mrirt_inject_predict_volume(const MrirtInjectDesc* desc, const float* B, con
 int64_t mrirt_boundary_weights_scratch_bytes(const uint32_t hwd[3]);
 int mrirt_boundary_weights(const int16_t* labels, const uint32_t hwd[3], uint32_t num_classes, float* out, void* scratch,
                            int64_t scratch_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------ */
+/* Coordinate-injection INR: training step (gradients to every W_l, b_l and to B)        */
+/* ------------------------------------------------------------------------------------ */
+/* Added within ABI 4: three symbols, no new struct.  csrc/inr_inject_train.hip; DESIGN.md section 24.
+ * The conventions are those of the section above and of mrirt_inr_forward_f32 / mrirt_inr_loss / mrirt_inr_backward: device
+ * pointers (desc and dropout excepted), a chain of launches on `stream`, no host synchronisation, no allocation, no float
+ * atomics, one writer per element: the same inputs give the same bits.  One scratch of mrirt_inject_train_scratch_bytes(desc,
+ * n) bytes (16-byte aligned; monotone in n; 0 for a refused desc or n) serves forward, loss and backward: its first
+ * mrirt_inr_loss_scratch_bytes(n) bytes are the scratch of mrirt_inr_loss, which may be called between the two on the same
+ * buffer; behind them lie the features [n][F], every hidden activation after dropout ([n][width[l]] each), dz ping and pong
+ * ([n][max hidden width] each), the feature gradient [n][F], c01 [n][3] and min(ceil(n / 256), 64) slabs of
+ * max(max_l (in_l + 1) out_l, 3 F / 2) floats, every region aligned to 256 bytes.
+ * Refused before anything is launched: MRIRT_ERR_NULL for a NULL desc, B, w, b, coords, mods (unless numMods == 0), logits /
+ * dlogits, grad_B, grad_w, grad_b or scratch; MRIRT_ERR_ARG for what mrirt_inject_forward refuses of desc, n and dropout
+ * (samples must be 1), a flags bit other than bit 0, a misaligned or too-small scratch.
+ *
+ * forward_train: exactly mrirt_inject_forward with the same arguments -- logits [n][C] are the same bits -- and the features
+ *   and each layer's post-dropout activation h_l stay in the scratch.  dropout NULL or keep == 1: no mask.
+ * backward: must follow forward_train on the same scratch and be given the same B, w, coords, mods and dropout (it reads
+ *   only keep: scale = 1.0f / keep as in the forward; no Philox word is drawn).  With x_l = [h_{l-1} | coords | mods] as the
+ *   forward formed it (x_0 = [s, k, mods]), dz_{L-1} = dlogits, and for l = L - 1 .. 0:
+ *     dW_l[i][j] = sum_p x_l[p][i] dz_l[p][j],  db_l[j] = sum_p dz_l[p][j]: slab z covers the points [z len, (z + 1) len), len =
+ *       256 doubled until at most 64 slabs cover n; inside a slab the products are summed in increasing p from +0 on
+ *       v_mfma_f32_16x16x4_f32; the slabs are added 0, 1, 2, .. (from +0, or from the old value with flags bit 0)
+ *     l >= 1:  dh[p][i] = sum_j dz_l[p][j] W_l[i][j], j ascending, for i < width[l - 1] only (the injected rows get no
+ *       gradient);  dz_{l-1}[p][i] = dh[p][i] * scale where the saved h_{l-1}[p][i] > 0, else +0 (no multiplication without
+ *       dropout; as scale >= 1, "kept and z > 0" is "saved value > 0"; a NaN activation passes no gradient)
+ *     l == 0:  dF[p][i] = sum_j dz_0[p][j] W_0[i][j], i < F;   g[p][j] = (dF[p][j] * k_pj) - (dF[p][F / 2 + j] * s_pj), and g = +0
+ *       where !(|a_j| <= 2^20), a_j recomputed from B and coords as the features compute it (there the feature is a constant);
+ *       dB[j][a] = 6.2831855f * (sum_p g[p][j] c01[p][a]), the sum in slab order, the constant applied once to the finished
+ *       sum before it is added to an old value (flags bit 0)
+ *   grad_B [F / 2][3]; grad_w, grad_b in the flat unpadded layouts of w and b.  flags bit 0: accumulate into the three.
+ *   No gradient reaches coords or mods. */
+int64_t mrirt_inject_train_scratch_bytes(const MrirtInjectDesc* desc, int64_t n);
+int mrirt_inject_forward_train(const MrirtInjectDesc* desc, const float* B, const float* w, const float* b,
+                               const float* coords, const float* mods, int64_t n, const MrirtInjectDropout* dropout,
+                               float* logits, void* scratch, int64_t scratch_bytes, void* stream);
+int mrirt_inject_backward(const MrirtInjectDesc* desc, const float* B, const float* w, const float* coords,
+                          const float* mods, int64_t n, const MrirtInjectDropout* dropout, const float* dlogits,
+                          float* grad_B, float* grad_w, float* grad_b, uint32_t flags,
+                          void* scratch, int64_t scratch_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------ */
 /* Misc                                                                                  */

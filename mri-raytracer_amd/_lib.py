@@ -17,7 +17,7 @@ CSRC = PKG_DIR / "csrc"
 INCLUDE = PKG_DIR.parent / "include"
 SO_PATH = pathlib.Path(os.environ.get("MRIRT_LIB", PKG_DIR / "libmrirt.so"))   # override: A/B builds in development
 HIP_SOURCES = ["brats_march.hip", "brats_order.hip", "brats_skip.hip", "brats_c5.hip", "brats_slab.hip", "brats_ring.hip", "brats_backward.hip", "brats_soft.hip", "brats_tf.hip", "volume_march.hip", "grid_ops.hip", "inr_mlp.hip",
-               "inr_stream.hip", "inr_ws.hip", "inr_refine.hip", "inr_train.hip", "inr_optim.hip", "inr_muon.hip", "inr_lossx.hip", "inr_inject.hip", "mesh_rt.hip", "edt.hip", "surface.hip", "prep.hip", "components.hip", "abort_trace.cpp"]
+               "inr_stream.hip", "inr_ws.hip", "inr_refine.hip", "inr_train.hip", "inr_optim.hip", "inr_muon.hip", "inr_lossx.hip", "inr_inject.hip", "inr_inject_train.hip", "mesh_rt.hip", "edt.hip", "surface.hip", "prep.hip", "components.hip", "abort_trace.cpp"]
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17", "-Wall"]
 
 # every extern "C" symbol include/mrirt.h declares
@@ -48,6 +48,7 @@ ABI_SYMBOLS = [
     "mrirt_render_brats_tf",
     "mrirt_inject_scratch_bytes", "mrirt_inject_forward", "mrirt_inject_uncertainty", "mrirt_inject_predict_volume",
     "mrirt_boundary_weights_scratch_bytes", "mrirt_boundary_weights",
+    "mrirt_inject_train_scratch_bytes", "mrirt_inject_forward_train", "mrirt_inject_backward",
 ]
 
 ABI_VERSION = 4          # MRIRT_ABI_VERSION of include/mrirt.h this binding was written against
@@ -501,6 +502,12 @@ def lib() -> C.CDLL:
     l.mrirt_inject_uncertainty.restype = i32
     l.mrirt_inject_predict_volume.argtypes = [*inj, vp, C.POINTER(u32), i64, C.POINTER(InjectDropout), vp, vp, vp, i64, vp]
     l.mrirt_inject_predict_volume.restype = i32
+    l.mrirt_inject_train_scratch_bytes.argtypes = [C.POINTER(InjectDesc), i64]
+    l.mrirt_inject_train_scratch_bytes.restype = i64
+    l.mrirt_inject_forward_train.argtypes = [*inj, vp, vp, i64, C.POINTER(InjectDropout), vp, vp, i64, vp]
+    l.mrirt_inject_forward_train.restype = i32
+    l.mrirt_inject_backward.argtypes = [C.POINTER(InjectDesc), vp, vp, vp, vp, i64, C.POINTER(InjectDropout), vp, vp, vp, vp, u32, vp, i64, vp]
+    l.mrirt_inject_backward.restype = i32
     l.mrirt_boundary_weights_scratch_bytes.argtypes = [C.POINTER(u32)]
     l.mrirt_boundary_weights_scratch_bytes.restype = i64
     l.mrirt_boundary_weights.argtypes = [vp, C.POINTER(u32), u32, vp, vp, i64, vp]

@@ -8,12 +8,13 @@
 //   inj_point_kernel      per point over the logits: argmax, softmax added into the running sum, entropy of the mean
 //   inj_boundary_kernel   max over classes of 1 / (1 + sqrt(d2)) on the squared-distance field of csrc/edt.hip
 // No allocation, no host synchronisation, no float atomics, one writer per element: the same inputs give the same bits.
+// The feature and layer launches (inj_run_features, inj_run_layers; csrc/inr_inject_host.h) take their output buffers as
+// arguments: the training step of csrc/inr_inject_train.hip runs them into per-layer buffers.
 #include "inr_device.h"
 #include "inr_gemm.h"
-#include "inr_inject.h"
+#include "inr_inject_host.h"
 #include "edt_line.h"
 #include "siren_sincos.h"
-#include "mrirt_host.h"
 
 namespace mrirt {
 
@@ -188,9 +189,7 @@ __global__ __launch_bounds__(kInjThreads) void inj_boundary_kernel(const double*
 
 // ---- host ----------------------------------------------------------------------------------------------------------------------
 
-struct InjDrop { uint64_t seed, index0; uint32_t thr, s; float scale; bool on; };
-
-static int inj_desc(const MrirtInjectDesc* d, InjNet& N) {
+int inj_desc(const MrirtInjectDesc* d, InjNet& N) {
     if (!d) return MRIRT_ERR_NULL;
     if (d->numLayers < 2 || d->numLayers > kInjMaxLayers) return MRIRT_ERR_ARG;
     if (inj_check_shape(d->numLayers, d->fourierDim, d->numMods, d->width, d->coordLayers, d->modLayers) != 0) return MRIRT_ERR_ARG;
@@ -199,7 +198,7 @@ static int inj_desc(const MrirtInjectDesc* d, InjNet& N) {
 }
 
 // what every entry point refuses of a dropout struct; S: how many samples this call may take at most
-static int inj_check_dropout(const MrirtInjectDropout* p, uint32_t maxSamples) {
+int inj_check_dropout(const MrirtInjectDropout* p, uint32_t maxSamples) {
     if (!(p->keep > 0.0f && p->keep <= 1.0f) || !isfinite(1.0f / p->keep)) return MRIRT_ERR_ARG;
     if (p->samples < 1 || p->samples > maxSamples) return MRIRT_ERR_ARG;
     if (p->sample0 >= kInjMaxSampleIndex || p->sample0 + p->samples > kInjMaxSampleIndex) return MRIRT_ERR_ARG;
@@ -207,7 +206,7 @@ static int inj_check_dropout(const MrirtInjectDropout* p, uint32_t maxSamples) {
     return MRIRT_OK;
 }
 
-static InjDrop inj_drop(const MrirtInjectDropout* p, uint32_t s) {
+InjDrop inj_drop(const MrirtInjectDropout* p, uint32_t s) {
     InjDrop d = {};
     if (!p || p->keep == 1.0f) return d;                 // keep == 1 masks nothing: the evaluation forward
     d.on = true;
@@ -219,10 +218,10 @@ static InjDrop inj_drop(const MrirtInjectDropout* p, uint32_t s) {
 
 static uint32_t inj_blocks(int64_t items) { return (uint32_t)((items + kInjThreads - 1) / kInjThreads); }
 
-static int run_features(const InjNet& N, const InjLayout& Y, const float* B, const float* coords, int64_t n, int64_t base,
-                        const uint32_t* hwd, char* scratch, hipStream_t s) {
+int inj_run_features(const InjNet& N, const float* B, const float* coords, int64_t n, int64_t base, const uint32_t* hwd, float* coordsOut,
+                     float* feat, hipStream_t s) {
     InjFeatArgs f = {};
-    f.B = B; f.coordsIn = coords; f.coordsOut = (float*)(scratch + Y.offCoords); f.feat = (float*)(scratch + Y.offFeat);
+    f.B = B; f.coordsIn = coords; f.coordsOut = coordsOut; f.feat = feat;
     f.n = n; f.base = base; f.F = N.F;
     if (hwd) { f.H = hwd[0]; f.W = hwd[1]; f.D = hwd[2]; }
     hipLaunchKernelGGL(inj_features_kernel, dim3(inj_blocks(n * (int64_t)(N.F / 2))), dim3(kInjThreads), 0, s, f);
@@ -239,23 +238,36 @@ static int launch_layer(const InjGemmArgs& g, hipStream_t s) {
     return MRIRT_OK;
 }
 
-// the L layer launches over the features already in the scratch; coords: [n][3]; mods as inj_layer_view takes them
-static int run_layers(const InjNet& N, const InjLayout& Y, const float* w, const float* b, const float* coords, const float* mods,
-                      int64_t modRow, int64_t modCol, int64_t n, const InjDrop& d, float* logits, char* scratch, hipStream_t s) {
+// coords: [n][3]; mods as inj_layer_view takes them
+int inj_run_layers(const InjNet& N, const float* feat, float* const* act, const float* w, const float* b, const float* coords,
+                   const float* mods, int64_t modRow, int64_t modCol, int64_t n, const InjDrop& d, float* logits, hipStream_t s) {
     for (uint32_t l = 0; l < N.numLayers; ++l) {
         const bool head = l + 1 == N.numLayers;
-        const float* h = l == 0 ? (const float*)(scratch + Y.offFeat) : (const float*)(scratch + inj_act_offset(Y, l - 1));
+        const float* h = l == 0 ? feat : act[l - 1];
         InjGemmArgs g = {};
         g.A = inj_layer_view(N, l, n, h, coords, mods, modRow, modCol);
         g.B = TrView{ w + N.wOff[l], 1, (int64_t)N.out[l], N.out[l], 0u };
         g.M = (uint32_t)n; g.N = N.out[l]; g.K = N.in[l];
-        g.C = head ? logits : (float*)(scratch + inj_act_offset(Y, l));
+        g.C = head ? logits : act[l];
         g.bias = b + N.bOff[l];
         g.seed = d.seed; g.index0 = d.index0; g.ctr2 = 256u * d.s + l; g.thr = d.thr; g.scale = d.scale;
         const int rc = head ? launch_layer<kInjHead>(g, s) : d.on ? launch_layer<kInjDrop>(g, s) : launch_layer<kInjRelu>(g, s);
         if (rc != MRIRT_OK) return rc;
     }
     return MRIRT_OK;
+}
+
+// the two over the inference scratch: features at offFeat, the activations in the two alternating buffers
+static int run_features(const InjNet& N, const InjLayout& Y, const float* B, const float* coords, int64_t n, int64_t base,
+                        const uint32_t* hwd, char* scratch, hipStream_t s) {
+    return inj_run_features(N, B, coords, n, base, hwd, (float*)(scratch + Y.offCoords), (float*)(scratch + Y.offFeat), s);
+}
+
+static int run_layers(const InjNet& N, const InjLayout& Y, const float* w, const float* b, const float* coords, const float* mods,
+                      int64_t modRow, int64_t modCol, int64_t n, const InjDrop& d, float* logits, char* scratch, hipStream_t s) {
+    float* act[kInjMaxLayers];
+    for (uint32_t l = 0; l < kInjMaxLayers; ++l) act[l] = (float*)(scratch + inj_act_offset(Y, l));
+    return inj_run_layers(N, (const float*)(scratch + Y.offFeat), act, w, b, coords, mods, modRow, modCol, n, d, logits, s);
 }
 
 static int run_point(const InjPointArgs& p, hipStream_t s) {

@@ -1547,3 +1547,236 @@ def boundary_weights(seg, num_classes: int = 4) -> torch.Tensor:
         rc = lib.mrirt_boundary_weights(_ptr(lab), hwd, int(num_classes), _ptr(out), _ptr(scratch), nbytes, _stream_ptr(None))
     _lib.check(rc, "mrirt_boundary_weights")
     return out
+
+
+# ---- training the coordinate-injection INR (csrc/inr_inject_train.hip) -----------------------------------
+
+def _inject_in_dims(F: int, M: int, widths: Sequence[int], coord_layers, mod_layers) -> List[int]:
+    L = len(widths)
+    cl = {int(v) for v in coord_layers if 0 < int(v) < L - 1}
+    ml = {int(v) for v in mod_layers if 0 < int(v) < L - 1}
+    return [F + M if l == 0 else widths[l - 1] + (3 if l in cl else 0) + (M if l in ml else 0) for l in range(L)]
+
+
+def inject_init(seed: int, fourier_dim: int = 128, num_mods: int = 4, hidden_dims: Sequence[int] = (64, 64, 64), out_dim: int = 4,
+                coord_layers=(1, 2, 3), mod_layers=(2,), sigma: float = 5.0, voxel_spacing=(1.0, 1.0, 1.0)) -> Dict[str, Any]:
+    """The notebook's initial ``params`` (cells 6 - 7) with a NumPy generator: ``{"fourier": {"B"}, "mlp": [{"W", "b"}, ...]}``,
+    ``B ~ N(0, sigma) / voxel_spacing`` of shape (fourier_dim / 2, 3), Glorot-uniform weights over the injected input widths,
+    zero biases.  The library's own rule, as ``init_mlp`` and ``siren_init``: JAX's key stream is not reproduced."""
+    rng = np.random.default_rng(int(seed))
+    F, M = int(fourier_dim), int(num_mods)
+    widths = [int(h) for h in hidden_dims] + [int(out_dim)]
+    B = rng.normal(0.0, 1.0, (F // 2, 3)) * float(sigma) / np.asarray(voxel_spacing, np.float64).reshape(1, 3)
+    mlp = []
+    for a, b in zip(_inject_in_dims(F, M, widths, coord_layers, mod_layers), widths):
+        lim = np.sqrt(6.0 / (a + b))
+        mlp.append({"W": rng.uniform(-lim, lim, (a, b)).astype(np.float32), "b": np.zeros(b, np.float32)})
+    return {"fourier": {"B": B.astype(np.float32)}, "mlp": mlp}
+
+
+def inject_train_scratch(desc: _lib.InjectDesc, n: int, dev) -> torch.Tensor:
+    """The step's scratch (``mrirt_inject_train_scratch_bytes``) as a uint8 tensor: forward, loss and backward share it."""
+    nbytes = int(_lib.lib().mrirt_inject_train_scratch_bytes(C.byref(desc), int(n)))
+    if nbytes <= 0:
+        raise _lib.MrirtError(-5, "mrirt_inject_train_scratch_bytes")
+    return torch.empty(nbytes, dtype=torch.uint8, device=dev)
+
+
+def inject_forward_train(desc: _lib.InjectDesc, B: torch.Tensor, w_flat: torch.Tensor, b_flat: torch.Tensor, coords: torch.Tensor, mods,
+                         n: int, scratch: torch.Tensor, dropout: Optional[_lib.InjectDropout] = None) -> torch.Tensor:
+    """``mrirt_inject_forward_train``: the logits (n, C) of ``mrirt_inject_forward``, bit for bit; the features and every
+    post-dropout activation stay in ``scratch`` for ``inject_backward``."""
+    logits = torch.empty((int(n), desc.width[desc.numLayers - 1]), dtype=torch.float32, device=w_flat.device)
+    rc = _lib.lib().mrirt_inject_forward_train(C.byref(desc), _ptr(B), _ptr(w_flat), _ptr(b_flat), _ptr(coords),
+                                               _ptr(mods) if mods is not None else None, int(n),
+                                               C.byref(dropout) if dropout is not None else None, _ptr(logits), _ptr(scratch),
+                                               scratch.numel(), _stream_ptr(None))
+    _lib.check(rc, "mrirt_inject_forward_train")
+    return logits
+
+
+def inject_backward(desc: _lib.InjectDesc, B: torch.Tensor, w_flat: torch.Tensor, coords: torch.Tensor, mods, n: int, dlogits: torch.Tensor,
+                    scratch: torch.Tensor, dropout: Optional[_lib.InjectDropout] = None, grad_B: Optional[torch.Tensor] = None,
+                    grad_w: Optional[torch.Tensor] = None, grad_b: Optional[torch.Tensor] = None, accumulate: bool = False):
+    """``mrirt_inject_backward``: (grad_B (F / 2, 3), grad_w, grad_b in the flat layouts of the weights / biases) from what
+    ``inject_forward_train`` left in ``scratch``; ``dropout`` must be the forward's.  ``accumulate`` adds into the given buffers."""
+    dev = w_flat.device
+    nb = sum(desc.width[l] for l in range(desc.numLayers))
+    grad_B = torch.empty_like(B) if grad_B is None else grad_B
+    grad_w = torch.empty_like(w_flat) if grad_w is None else grad_w
+    grad_b = torch.empty(nb, dtype=torch.float32, device=dev) if grad_b is None else grad_b
+    rc = _lib.lib().mrirt_inject_backward(C.byref(desc), _ptr(B), _ptr(w_flat), _ptr(coords), _ptr(mods) if mods is not None else None, int(n),
+                                          C.byref(dropout) if dropout is not None else None, _ptr(dlogits), _ptr(grad_B), _ptr(grad_w),
+                                          _ptr(grad_b), 1 if accumulate else 0, _ptr(scratch), scratch.numel(), _stream_ptr(None))
+    _lib.check(rc, "mrirt_inject_backward")
+    return grad_B, grad_w, grad_b
+
+
+def _inject_split(desc: _lib.InjectDesc, t_B: torch.Tensor, t_w: torch.Tensor, t_b: torch.Tensor) -> Dict[str, Any]:
+    """Flat (B, w, b) tensors as views in ``params``' structure."""
+    L, F, M = desc.numLayers, desc.fourierDim, desc.numMods
+    widths = [desc.width[l] for l in range(L)]
+    ins = _inject_in_dims(F, M, widths, [l for l in range(L) if (desc.coordLayers >> l) & 1], [l for l in range(L) if (desc.modLayers >> l) & 1])
+    mlp, wo, bo = [], 0, 0
+    for a, b in zip(ins, widths):
+        mlp.append({"W": t_w[wo:wo + a * b].view(a, b), "b": t_b[bo:bo + b]})
+        wo, bo = wo + a * b, bo + b
+    return {"fourier": {"B": t_B.view(F // 2, 3)}, "mlp": mlp}
+
+
+def make_inject_loss_and_grad(num_classes: int, class_weights, dice_weight: float, coord_layers=(1, 2, 3), mod_layers=(2,),
+                              ext: Optional[_lib.InrLossExt] = None):
+    """``jax.value_and_grad(loss_fn, has_aux=True)`` for the coordinate-injection network with the library's loss: returns
+    ``fn(params, coords, mods, labels, dropout=None) -> ((loss, aux), grads)``; ``loss`` a 0-d device tensor, ``aux =
+    {"ce_per_class", "dice_per_class"}`` and ``grads`` device tensors in ``params``' structure (``{"fourier": {"B"}, "mlp":
+    [{"W", "b"}]}``).  One ``mrirt_inject_forward_train``, ``mrirt_inr_loss`` (``mrirt_inr_loss_ext`` with ``ext``, which adds
+    ``aux["terms"]``) and one ``mrirt_inject_backward``; nothing synchronises with the host."""
+    cw = [float(v) for v in np.asarray(class_weights, dtype=np.float32).reshape(-1)]
+    if len(cw) != int(num_classes):
+        raise ValueError(f"class_weights holds {len(cw)} values for {num_classes} classes")
+
+    def loss_and_grad(params, coords, mods, labels, dropout=None):
+        dev = _require_gpu()
+        desc = inject_desc(params, coord_layers, mod_layers)
+        if desc.width[desc.numLayers - 1] != int(num_classes):
+            raise ValueError(f"the network has {desc.width[desc.numLayers - 1]} outputs for {num_classes} classes")
+        c, m = _inject_points(coords, mods, dev, desc.numMods)
+        n = int(c.shape[0])
+        B, w, b = _inject_flat(params, dev)
+        lab = torch.as_tensor(labels).to(dev).to(torch.int32).contiguous()
+        scratch = inject_train_scratch(desc, n, dev)
+        logits = inject_forward_train(desc, B, w, b, c, m, n, scratch, dropout)
+        loss, aux, dl, *terms = loss_and_dlogits(logits, lab, cw, dice_weight, scratch, ext=ext)
+        gB, gw, gb = inject_backward(desc, B, w, c, m, n, dl, scratch, dropout)
+        return (loss, {"ce_per_class": aux[0], "dice_per_class": aux[1], **({"terms": terms[0]} if terms else {})}), _inject_split(desc, gB, gw, gb)
+
+    return loss_and_grad
+
+
+class _InjectStep(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, coords, mods, coord_layers, mod_layers, dropout, num_layers, B, *wb):
+        Ws, bs = wb[:num_layers], wb[num_layers:]
+        params = {"fourier": {"B": B.detach()}, "mlp": [{"W": W.detach(), "b": b.detach()} for W, b in zip(Ws, bs)]}
+        desc = inject_desc(params, coord_layers, mod_layers)
+        dev = B.device
+        n = int(coords.shape[0])
+        Bf = B.detach().to(torch.float32).contiguous()
+        w_flat = torch.cat([W.detach().to(torch.float32).reshape(-1) for W in Ws])
+        b_flat = torch.cat([b.detach().to(torch.float32).reshape(-1) for b in bs])
+        scratch = inject_train_scratch(desc, n, dev)
+        logits = inject_forward_train(desc, Bf, w_flat, b_flat, coords, mods, n, scratch, dropout)
+        ctx.saved = (desc, Bf, w_flat, coords, mods, n, scratch, dropout)
+        return logits
+
+    @staticmethod
+    def backward(ctx, grad_logits):
+        desc, Bf, w_flat, coords, mods, n, scratch, dropout = ctx.saved
+        gB, gw, gb = inject_backward(desc, Bf, w_flat, coords, mods, n, grad_logits.to(torch.float32).contiguous(), scratch, dropout)
+        g = _inject_split(desc, gB, gw, gb)
+        return (None, None, None, None, None, None, g["fourier"]["B"], *[x["W"] for x in g["mlp"]], *[x["b"] for x in g["mlp"]])
+
+
+def inject_autograd(B, Ws, bs, coords, mods, coord_layers=(1, 2, 3), mod_layers=(2,), dropout: Optional[_lib.InjectDropout] = None) -> torch.Tensor:
+    """Differentiable fp32 logits (n, C) of the coordinate-injection network: the forward is ``mrirt_inject_forward_train``,
+    the backward ``mrirt_inject_backward`` -- gradients reach ``B`` (F / 2, 3), ``Ws`` (each (in, out)) and ``bs``, none the
+    inputs, so any torch loss and optimiser can fit the network."""
+    dev = B.device
+    M = int(Ws[0].shape[0]) - 2 * int(B.shape[0])
+    c, m = _inject_points(coords, mods, dev, max(M, 0))
+    return _InjectStep.apply(c, m, tuple(coord_layers), tuple(mod_layers), dropout, len(Ws), B, *Ws, *bs)
+
+
+def two_stage_schedule(stage1_steps: int, stage2_steps: int, lr_stage1: float, lr_stage2: float, warmup_steps: int, min_lr: float):
+    """The notebook's two-stage rate (cell 11) as ``schedule(step) -> float`` in host fp64: a linear warm-up to ``lr_stage1``,
+    a linear blend to ``lr_stage2`` at ``stage1_steps``, then to ``min_lr`` over ``stage2_steps``.  With ``stage2_steps == 0``
+    the last stage is never evaluated below ``stage1_steps``; from there on the rate is ``min_lr``."""
+    s1, s2, warm = int(stage1_steps), int(stage2_steps), int(warmup_steps)
+    lr1, lr2, lo = float(lr_stage1), float(lr_stage2), float(min_lr)
+
+    def schedule(step):
+        if step < warm:
+            return lr1 * (step / warm)
+        if step < s1:
+            u = (step - warm) / (s1 - warm)
+            return lr1 * (1.0 - u) + lr2 * u
+        if s2 == 0:
+            return lo
+        u = (step - s1) / s2
+        return lr2 * (1.0 - u) + lo * u
+
+    return schedule
+
+
+def inject_save(path, params) -> None:
+    """The notebook's flat checkpoint (cell 14: ``fourier_B``, ``mlp_W_i``, ``mlp_b_i``), which ``inject_load`` reads back."""
+    flat = {"fourier_B": _inject_np(params["fourier"]["B"])}
+    for i, layer in enumerate(params["mlp"]):
+        flat[f"mlp_W_{i}"], flat[f"mlp_b_{i}"] = _inject_np(layer["W"]), _inject_np(layer["b"])
+    np.savez_compressed(path, **flat)
+
+
+def train_inject(config: Dict[str, Any], cases_or_cache, params=None, log=None, save_path=None):
+    """The notebook's training loop (cells 11 - 13) over the library's calls, with its config keys: FOURIER_DIM, HIDDEN_DIMS,
+    COORD_INJECTION_LAYERS, MODALITY_INJECTION_LAYERS, DROPOUT_RATE, MICRO_BATCH_SIZE, ACCUM_STEPS, STAGE1_STEPS, STAGE2_STEPS,
+    LR_STAGE1, LR_STAGE2, MIN_LR, WARMUP_STEPS, WEIGHT_DECAY, CLIP_NORM, CLASS_WEIGHTS (and NUM_CLASSES, DICE_WEIGHT, RNG_SEED as
+    ``train_inr`` reads them; the optional FOCAL_GAMMA ... TUMOR_RATIO keys of ``loss_ext_of_config`` switch to
+    ``mrirt_inr_loss_ext`` and the tumour-ratio sampler).  Step ``t`` (0-based) of STAGE1_STEPS + STAGE2_STEPS runs ACCUM_STEPS
+    micro-batches -- ``VoxelCache.sample(RNG_SEED, g, MICRO_BATCH_SIZE)`` with ``g`` the global micro-batch index,
+    ``mrirt_inject_forward_train`` (dropout at keep ``1 - DROPOUT_RATE`` only for ``t > WARMUP_STEPS``, as cell 12 has it, with
+    ``sample0 = g`` and ``index0 = 0``), the loss, ``mrirt_inject_backward`` accumulating after the first -- and one
+    ``mrirt_inr_adamw_step`` over the flat parameters ``[w | B]`` and ``b`` with ``gscale = 1 / ACCUM_STEPS``, ``clipNorm =
+    CLIP_NORM`` and the rate of ``two_stage_schedule`` at ``t``.  The notebook's unified loss, hybrid sampler and coordinate
+    noise are not part of it.  ``save_path``: a directory; ``model_final.npz`` (the notebook's layout) is written there.
+    Returns ``(params, state)``: NumPy ``params`` and a dict with ``loss_history`` and ``opt`` (the ``AdamWState`` over
+    ``[w | B]`` and ``b``)."""
+    nc, seed = int(config["NUM_CLASSES"]), int(config["RNG_SEED"])
+    micro, accum = int(config["MICRO_BATCH_SIZE"]), int(config["ACCUM_STEPS"])
+    warmup, total = int(config["WARMUP_STEPS"]), int(config["STAGE1_STEPS"]) + int(config["STAGE2_STEPS"])
+    if micro < 1 or accum < 1 or total < 1:
+        raise ValueError("MICRO_BATCH_SIZE, ACCUM_STEPS and STAGE1_STEPS + STAGE2_STEPS must be positive")
+    cl, ml = tuple(config["COORD_INJECTION_LAYERS"]), tuple(config["MODALITY_INJECTION_LAYERS"])
+    schedule = two_stage_schedule(config["STAGE1_STEPS"], config["STAGE2_STEPS"], config["LR_STAGE1"], config["LR_STAGE2"], warmup, config["MIN_LR"])
+    keep = float(np.float32(1.0) - np.float32(config["DROPOUT_RATE"]))
+    ext_keys = _ext_keys_of(config)
+    ext = loss_ext_of_config(config, nc) if ext_keys else None
+    cache = cases_or_cache if isinstance(cases_or_cache, VoxelCache) else VoxelCache(cases_or_cache)
+    n_tumour = n_tumour_of(micro, config.get("TUMOR_RATIO", 0.0)) if ext_keys else 0
+    dev = cache.device
+    if params is None:
+        params = inject_init(seed, int(config["FOURIER_DIM"]), cache.n_modalities, config["HIDDEN_DIMS"], nc, cl, ml)
+    desc = inject_desc(params, cl, ml)
+    if desc.numMods != cache.n_modalities or desc.width[desc.numLayers - 1] != nc:
+        raise ValueError(f"the parameters take {desc.numMods} modalities and give {desc.width[desc.numLayers - 1]} classes; the cache holds "
+                         f"{cache.n_modalities}, the config asks for {nc}")
+    B, w, b = _inject_flat(params, dev)
+    nw = w.numel()
+    wB = torch.cat([w, B.reshape(-1)])                   # one flat allocation [w | B]: one optimiser call updates everything
+    st = AdamWState([], wB, b, torch.zeros_like(wB), torch.zeros_like(b), torch.zeros_like(wB), torch.zeros_like(b), 0)
+    gwB, gb = torch.empty_like(wB), torch.empty_like(b)
+    scratch = inject_train_scratch(desc, micro, dev)
+    cw = [float(v) for v in config["CLASS_WEIGHTS"]]
+    loss_history: List[Any] = []
+    for t in range(total):
+        losses = []
+        for k in range(accum):
+            g = t * accum + k
+            c, m, lab = cache.sample(seed, g, micro, n_tumour)
+            drop = inject_dropout(seed, keep, 1, g, 0) if t > warmup else None
+            m = m if desc.numMods else None
+            logits = inject_forward_train(desc, wB[nw:], wB[:nw], b, c, m, micro, scratch, drop)
+            loss, _, dl, *_ = loss_and_dlogits(logits, lab, cw, float(config["DICE_WEIGHT"]), scratch, ext=ext)
+            inject_backward(desc, wB[nw:], wB[:nw], c, m, micro, dl, scratch, drop, gwB[nw:], gwB[:nw], gb, accumulate=k > 0)
+            losses.append(loss)
+        adamw_step(st, gwB, gb, schedule(t), 1.0 / accum, float(config["CLIP_NORM"]), weight_decay=float(config["WEIGHT_DECAY"]))
+        loss_history.append(torch.stack(losses).mean())      # stays on the device: without a log nothing waits for a step
+        if log is not None:
+            log(t + 1, {"train/loss": float(loss_history[-1]), "train/step": t + 1, "train/lr": schedule(t)})
+    loss_history = [float(v) for v in torch.stack(loss_history).cpu()]
+    out = _inject_split(desc, wB[nw:].clone(), wB[:nw].clone(), b.clone())
+    out = {"fourier": {"B": _inject_np(out["fourier"]["B"])}, "mlp": [{"W": _inject_np(p["W"]), "b": _inject_np(p["b"])} for p in out["mlp"]]}
+    if save_path is not None:
+        save_path = pathlib.Path(save_path)
+        save_path.mkdir(parents=True, exist_ok=True)
+        inject_save(save_path / "model_final.npz", out)
+    return out, {"params": out, "train_cache": cache, "loss_history": loss_history, "opt": st, "save_path": save_path}
