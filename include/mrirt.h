@@ -52,7 +52,9 @@ extern "C" {
  *    the coordinate-injection INR: MrirtInjectDesc, MrirtInjectDropout (mrirt_sizeof(17), (18)), mrirt_inject_scratch_bytes,
  *    mrirt_inject_forward, mrirt_inject_uncertainty, mrirt_inject_predict_volume, mrirt_boundary_weights_scratch_bytes,
  *    mrirt_boundary_weights;
- *    its training step (no new struct): mrirt_inject_train_scratch_bytes, mrirt_inject_forward_train, mrirt_inject_backward. */
+ *    its training step (no new struct): mrirt_inject_train_scratch_bytes, mrirt_inject_forward_train, mrirt_inject_backward;
+ *    the notebook's unified loss and the samplers' field gather: MrirtUnifiedLoss (mrirt_sizeof(20)),
+ *    mrirt_unified_loss_scratch_bytes, mrirt_unified_loss, mrirt_inr_sample_field. */
 #define MRIRT_ABI_VERSION 4
 
 typedef enum MrirtStatus {
@@ -1115,6 +1117,61 @@ int mrirt_inject_backward(const MrirtInjectDesc* desc, const float* B, const flo
                           void* scratch, int64_t scratch_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------ */
+/* Unified focal + Dice + TV + boundary loss; the samplers' field gather                 */
+/* ------------------------------------------------------------------------------------ */
+/* Added within ABI 4: three symbols and one new struct, mrirt_sizeof(20) (19 stays 0).  csrc/inr_unified.hip; DESIGN.md
+ * section 25.  The loss of the reference's notebooks/improved.ipynb, cell 8, after the forward: logits [n][C], labels [n],
+ * boundary weights [n] (or NULL) -> loss [1], aux [8 + C], dlogits [n][C] (or NULL).  It stands where mrirt_inr_loss stands
+ * between mrirt_inject_forward_train and mrirt_inject_backward, with a scratch of its own.  Device pointers (cfg excepted),
+ * three launches on `stream` (two without dlogits), no host synchronisation, no allocation, no float atomics, one writer per
+ * element: the same inputs give the same bits.
+ *
+ * Per point, in fp32, with t_k = [label == k] (all 0 for a label outside 0..C-1; no label indexes memory):
+ *   zc = clip(z, -10, 10);  ps = softmax(zc);  pc = clip(ps, 1e-7f, 1 - 1e-7f);  pu = softmax(z);  am = first index of max z
+ * Sums over the batch, fp64, per-block then in block order:
+ *   P_k = sum pc_k   A_k = sum pc_k t_k   T_k = sum t_k   S_k = sum pu_k   Q_k = sum pu_k^2
+ *   FL = sum (1 - pc_y + 1e-7)^gamma (-log(pc_y + 1e-10))     (y the label; 0 for a label outside the range)
+ *   Bd = sum boundary_w |am - label|  (0 with a NULL boundary_w)     Acc = sum [am == label]
+ * Then, in fp64:
+ *   TI_k = clip(A_k / (A_k + alpha (P_k - A_k) + beta (T_k - A_k) + 1e-7), 0, 1);  mFTL = mean_k (1 - TI_k + 1e-7)^(1 / gamma)
+ *   mFL = FL / n;  ufl = clip(lambda mFTL + (1 - lambda) mFL, 0, 1e6)
+ *   dice_k = (2 A_k + 1) / (P_k + T_k + 1);  dl = clip(1 - sum_k dice_k cw_k / (sum_k cw_k + 1e-10), 0, 10)
+ *   tv = sum_k (Q_k / n - (S_k / n)^2);  bl = Bd / n
+ *   loss = uflWeight ufl + diceWeight dl + tvWeight tv + boundaryWeight bl
+ *   aux = [ufl, mFTL, mFL, dl, tv, bl, mean_{k >= 1} dice_k (0 for C == 1), Acc / n, dice_0 .. dice_{C-1}]
+ * The notebook's UNIFIED_FOCAL_DELTA is passed to its loss and never read; it has no member here.
+ * dlogits is the exact derivative of `loss`: the pc paths through the softmax Jacobian over zc, tv through the one over z.  A clip
+ * passes the gradient where lo <= x <= hi and none outside (at an exact tie JAX halves it); the two scalar clips pass none when
+ * active; the boundary term and Acc have none (argmax has none).
+ * A row holding a logit that is not finite (NaN, +-inf) takes no part: it adds nothing to any sum -- Acc and Bd included, n stays
+ * the divisor -- and its dlogits row is +0, so loss, aux and every other row are those of the batch with that row's terms
+ * removed.  Finite logits give finite outputs.
+ * Refused before anything is launched, in this order: MRIRT_ERR_NULL for a NULL logits, labels, cfg, loss, aux or scratch;
+ * MRIRT_ERR_ARG for n outside 1..2^31-1, num_classes outside 1..16, gamma outside [0.25, 1] (the focal derivative gamma
+ * base^(gamma - 1) stays bounded there), lambda outside [0, 1], a negative or non-finite tverskyAlpha, tverskyBeta, weight or
+ * class weight read, flags != 0, a scratch that is not 16-byte aligned or smaller than mrirt_unified_loss_scratch_bytes(n)
+ * (doubles: [min(ceil(n / 256), 256)] rows of 83 partial sums, the totals, the gradient's coefficients; aligned to 256 bytes;
+ * monotone in n; 0 for a refused n). */
+typedef struct MrirtUnifiedLoss {
+    float classWeights[16];     /* first C read (Dice) */
+    float gamma, lambda;        /* UNIFIED_FOCAL_GAMMA, UNIFIED_FOCAL_LAMBDA */
+    float tverskyAlpha, tverskyBeta;   /* the notebook's 0.3, 0.7 */
+    float uflWeight, diceWeight;       /* the notebook's 0.5, 0.5 */
+    float tvWeight, boundaryWeight;
+    uint32_t flags;             /* must be 0 */
+} MrirtUnifiedLoss;
+int64_t mrirt_unified_loss_scratch_bytes(int64_t n);
+int mrirt_unified_loss(const float* logits, const int32_t* labels, const float* boundary_w /* [n] or NULL */, int64_t n,
+                       uint32_t num_classes, const MrirtUnifiedLoss* cfg, float* loss, float* aux /* [8 + C] */,
+                       float* dlogits /* [n][C] or NULL */, void* scratch, int64_t scratch_bytes, void* stream);
+/* out[i] = fields[case_i][voxel_i], the voxel mrirt_inr_sample_batch draws for point i of (seed, batch_index) when n_tumour == 0
+ * and mrirt_inr_sample_batch_mix draws otherwise (the same Philox words through the same functions; one launch).  fields: a
+ * device table of cache->ncases device pointers to H W D floats each, in seg's voxel order (the boundary maps of
+ * mrirt_boundary_weights, for one).  Refusals: the mixed sampler's, plus MRIRT_ERR_NULL for a NULL fields or out. */
+int mrirt_inr_sample_field(const MrirtInrCache* cache, const MrirtInrTumourIndex* tumour, const float* const* fields, uint64_t seed,
+                           uint64_t batch_index, int64_t n, int64_t n_tumour, float* out, void* stream);
+
+/* ------------------------------------------------------------------------------------ */
 /* Misc                                                                                  */
 /* ------------------------------------------------------------------------------------ */
 int mrirt_abi_version(void);
@@ -1123,8 +1180,8 @@ int mrirt_last_hip_error(void);            /* hipError_t of the last failed HIP 
 uint32_t mrirt_sizeof(uint32_t which);     /* 0 BratsParams, 1 RenderExt, 2 VolumeParams, 3 SdfParams, 4 InrDesc, 5 Skip,
                                               6 MeshParams, 7 InrCache, 8 AdamW, 9 InrTrainCfg, 10 InrTrainState,
                                               11 Muon, 13 InrLossExt, 14 InrTumourIndex, 15 InrTrainExt, 17 InjectDesc,
-                                              18 InjectDropout; 12 and 16 are unassigned and stay 0, as every index
-                                              beyond 18 */
+                                              18 InjectDropout, 20 UnifiedLoss; 12, 16 and 19 are unassigned and stay
+                                              0, as every index beyond 20 */
 /* Opt-in diagnostics (host only; the library installs nothing by itself): a SIGABRT handler that writes the native
  * backtrace of the aborting thread and, when file descriptor 2 has been redirected into a regular file (a test runner's
  * capture), the tail of that file to `fd` — a descriptor the caller duplicated before the redirection — and then chains

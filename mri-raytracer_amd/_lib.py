@@ -17,7 +17,7 @@ CSRC = PKG_DIR / "csrc"
 INCLUDE = PKG_DIR.parent / "include"
 SO_PATH = pathlib.Path(os.environ.get("MRIRT_LIB", PKG_DIR / "libmrirt.so"))   # override: A/B builds in development
 HIP_SOURCES = ["brats_march.hip", "brats_order.hip", "brats_skip.hip", "brats_c5.hip", "brats_slab.hip", "brats_ring.hip", "brats_backward.hip", "brats_soft.hip", "brats_tf.hip", "volume_march.hip", "grid_ops.hip", "inr_mlp.hip",
-               "inr_stream.hip", "inr_ws.hip", "inr_refine.hip", "inr_train.hip", "inr_optim.hip", "inr_muon.hip", "inr_lossx.hip", "inr_inject.hip", "inr_inject_train.hip", "mesh_rt.hip", "edt.hip", "surface.hip", "prep.hip", "components.hip", "abort_trace.cpp"]
+               "inr_stream.hip", "inr_ws.hip", "inr_refine.hip", "inr_train.hip", "inr_optim.hip", "inr_muon.hip", "inr_lossx.hip", "inr_inject.hip", "inr_inject_train.hip", "inr_unified.hip", "mesh_rt.hip", "edt.hip", "surface.hip", "prep.hip", "components.hip", "abort_trace.cpp"]
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17", "-Wall"]
 
 # every extern "C" symbol include/mrirt.h declares
@@ -49,6 +49,7 @@ ABI_SYMBOLS = [
     "mrirt_inject_scratch_bytes", "mrirt_inject_forward", "mrirt_inject_uncertainty", "mrirt_inject_predict_volume",
     "mrirt_boundary_weights_scratch_bytes", "mrirt_boundary_weights",
     "mrirt_inject_train_scratch_bytes", "mrirt_inject_forward_train", "mrirt_inject_backward",
+    "mrirt_unified_loss_scratch_bytes", "mrirt_unified_loss", "mrirt_inr_sample_field",
 ]
 
 ABI_VERSION = 4          # MRIRT_ABI_VERSION of include/mrirt.h this binding was written against
@@ -182,6 +183,12 @@ class InjectDesc(C.Structure):
 class InjectDropout(C.Structure):
     """MrirtInjectDropout: the Philox mask stream of one call."""
     _fields_ = [("seed", C.c_uint64), ("keep", f32), ("samples", u32), ("sample0", u32), ("reserved", u32), ("index0", C.c_uint64)]
+
+
+class UnifiedLoss(C.Structure):
+    """MrirtUnifiedLoss: the loss of notebooks/improved.ipynb, cell 8."""
+    _fields_ = [("classWeights", f32 * 16), ("gamma", f32), ("lambda_", f32), ("tverskyAlpha", f32), ("tverskyBeta", f32),
+                ("uflWeight", f32), ("diceWeight", f32), ("tvWeight", f32), ("boundaryWeight", f32), ("flags", u32)]
 
 
 class Skip(C.Structure):
@@ -512,6 +519,12 @@ def lib() -> C.CDLL:
     l.mrirt_boundary_weights_scratch_bytes.restype = i64
     l.mrirt_boundary_weights.argtypes = [vp, C.POINTER(u32), u32, vp, vp, i64, vp]
     l.mrirt_boundary_weights.restype = i32
+    l.mrirt_unified_loss_scratch_bytes.argtypes = [i64]
+    l.mrirt_unified_loss_scratch_bytes.restype = i64
+    l.mrirt_unified_loss.argtypes = [vp, vp, vp, i64, u32, C.POINTER(UnifiedLoss), vp, vp, vp, vp, i64, vp]
+    l.mrirt_unified_loss.restype = i32
+    l.mrirt_inr_sample_field.argtypes = [C.POINTER(InrCache), C.POINTER(InrTumourIndex), vp, u64, u64, i64, i64, vp, vp]
+    l.mrirt_inr_sample_field.restype = i32
     l.mrirt_status_string.argtypes = [i32]
     l.mrirt_status_string.restype = C.c_char_p
     l.mrirt_sizeof.argtypes = [u32]
@@ -528,7 +541,7 @@ def lib() -> C.CDLL:
                                 InrTrainState, Muon, None, InrLossExt, InrTumourIndex, InrTrainExt)):          # index 12 is unassigned
         if st is not None and l.mrirt_sizeof(which) != C.sizeof(st):
             raise ImportError(f"ABI mismatch: {st.__name__} is {C.sizeof(st)} B here, {l.mrirt_sizeof(which)} B in {SO_PATH}")
-    for which, st in ((17, InjectDesc), (18, InjectDropout)):                                              # 16 is unassigned
+    for which, st in ((17, InjectDesc), (18, InjectDropout), (20, UnifiedLoss)):                           # 16 and 19 are unassigned
         if l.mrirt_sizeof(which) != C.sizeof(st):
             raise ImportError(f"ABI mismatch: {st.__name__} is {C.sizeof(st)} B here, {l.mrirt_sizeof(which)} B in {SO_PATH}")
     _LIB = l

@@ -456,6 +456,7 @@ extern "C" uint32_t mrirt_sizeof(uint32_t which) {
         case 15: return (uint32_t)sizeof(MrirtInrTrainExt);
         case 17: return (uint32_t)sizeof(MrirtInjectDesc);          // 16 stays unassigned too
         case 18: return (uint32_t)sizeof(MrirtInjectDropout);
+        case 20: return (uint32_t)sizeof(MrirtUnifiedLoss);         // 19 stays unassigned too
         default: return 0;
     }
 }

@@ -834,6 +834,31 @@ class VoxelCache:
         _lib.check(rc, "mrirt_inr_sample_batch")
         return coords, feats, labels
 
+    def set_boundary(self, maps=None) -> List[torch.Tensor]:
+        """Give the cache the boundary weight maps of the notebook's cache (cell 5): ``maps`` a list of (H, W, D) fp32 volumes,
+        one per case, or None to build each with ``boundary_weights(seg)``.  The cache keeps the device copies and the table
+        of their pointers, which ``sample_field`` reads."""
+        if maps is None:
+            maps = [boundary_weights(s) for s in self.seg]
+        maps = [_dev_f32(m, self.device) for m in maps]
+        if len(maps) != self.n_cases or any(tuple(m.shape) != self.vol_shape for m in maps):
+            raise ValueError(f"set_boundary needs {self.n_cases} maps of shape {self.vol_shape}")
+        self.boundary = maps
+        self.boundary_table = torch.tensor([m.data_ptr() for m in maps], dtype=torch.int64, device=self.device)
+        return maps
+
+    def sample_field(self, seed: int, batch_index: int, n: int, n_tumour: int = 0) -> torch.Tensor:
+        """``mrirt_inr_sample_field``: the boundary map's values (n,) fp32 at the voxels ``sample(seed, batch_index, n,
+        n_tumour)`` draws, point by point.  ``set_boundary`` must have been called."""
+        if getattr(self, "boundary_table", None) is None:
+            raise ValueError("sample_field: call set_boundary() first")
+        out = torch.empty(int(n), dtype=torch.float32, device=self.device)
+        tumour = C.byref(self.tumour_index()) if int(n_tumour) != 0 else None
+        rc = _lib.lib().mrirt_inr_sample_field(C.byref(self.desc), tumour, _ptr(self.boundary_table), int(seed) & (2 ** 64 - 1),
+                                               int(batch_index) & (2 ** 64 - 1), int(n), int(n_tumour), _ptr(out), _stream_ptr(None))
+        _lib.check(rc, "mrirt_inr_sample_field")
+        return out
+
     def sample_voxels(self, case_indices, h_coords, w_coords, d_coords):
         """dataloader.py:86-96: (intensities (N, M) fp32, labels (N,) int16) of the given voxels, by plain indexing."""
         idx = [torch.as_tensor(np.asarray(v) if not isinstance(v, torch.Tensor) else v).to(self.device).to(torch.int64).reshape(-1)
@@ -1624,16 +1649,92 @@ def _inject_split(desc: _lib.InjectDesc, t_B: torch.Tensor, t_w: torch.Tensor, t
     return {"fourier": {"B": t_B.view(F // 2, 3)}, "mlp": mlp}
 
 
+# the notebook's own loss (csrc/inr_unified.hip)
+
+def unified_loss(class_weights, gamma: float = 0.5, lam: float = 0.5, alpha: float = 0.3, beta: float = 0.7, ufl_weight: float = 0.5,
+                 dice_weight: float = 0.5, tv_weight: float = 0.02, boundary_weight: float = 0.1) -> _lib.UnifiedLoss:
+    """``MrirtUnifiedLoss`` with the notebook's constants (cell 2: UNIFIED_FOCAL_GAMMA, UNIFIED_FOCAL_LAMBDA, TV_WEIGHT_STAGE1,
+    BOUNDARY_WEIGHT; cell 8: the Tversky 0.3 / 0.7 and the 0.5 / 0.5 mix).  UNIFIED_FOCAL_DELTA is not read by the notebook's
+    loss and has no member.  The library checks the values when the struct is used."""
+    x = _lib.UnifiedLoss()
+    cw = [float(np.float32(v)) for v in np.asarray(class_weights, dtype=np.float32).reshape(-1)]
+    if len(cw) > 16:
+        raise ValueError("at most 16 classes")
+    for k, v in enumerate(cw):
+        x.classWeights[k] = v
+    x.gamma, x.lambda_, x.tverskyAlpha, x.tverskyBeta = float(gamma), float(lam), float(alpha), float(beta)
+    x.uflWeight, x.diceWeight, x.tvWeight, x.boundaryWeight, x.flags = float(ufl_weight), float(dice_weight), float(tv_weight), float(boundary_weight), 0
+    return x
+
+
+def unified_loss_scratch(n: int, dev) -> torch.Tensor:
+    """The scratch of ``mrirt_unified_loss`` for ``n`` points (``mrirt_unified_loss_scratch_bytes``) as a uint8 tensor."""
+    nbytes = int(_lib.lib().mrirt_unified_loss_scratch_bytes(int(n)))
+    if nbytes <= 0:
+        raise _lib.MrirtError(-5, "mrirt_unified_loss_scratch_bytes")
+    return torch.empty(nbytes, dtype=torch.uint8, device=dev)
+
+
+def _unified_aux(aux: torch.Tensor) -> Dict[str, torch.Tensor]:
+    """aux [8 + C] of ``mrirt_unified_loss`` under the keys of the notebook's ``loss_fn`` (views, on the device)."""
+    keys = ("ufl", "mFTL", "mFL", "dice_loss", "tv_loss", "boundary_loss", "dice_mean_tumor", "accuracy")
+    return {**{k: aux[i] for i, k in enumerate(keys)}, "dice_per_class": aux[8:]}
+
+
+def unified_loss_and_dlogits(logits: torch.Tensor, labels: torch.Tensor, cfg: _lib.UnifiedLoss, boundary_w: Optional[torch.Tensor] = None,
+                             scratch: Optional[torch.Tensor] = None, want_grad: bool = True):
+    """``mrirt_unified_loss`` on (n, C) fp32 logits, int32 labels and (n,) fp32 boundary weights (or None): (loss 0-d, aux,
+    dlogits (n, C) or None), all on the device; ``aux`` is a dict with the keys of the notebook's ``loss_fn``: ufl, mFTL, mFL,
+    dice_loss, tv_loss, boundary_loss, dice_per_class (C,), dice_mean_tumor, accuracy.  ``scratch``: a uint8 tensor of at
+    least ``mrirt_unified_loss_scratch_bytes(n)`` bytes (``unified_loss_scratch``), allocated when None."""
+    n, nc = int(logits.shape[0]), int(logits.shape[1])
+    dev = logits.device
+    if boundary_w is not None and (boundary_w.dtype != torch.float32 or boundary_w.numel() != n or not boundary_w.is_contiguous()):
+        raise ValueError(f"boundary_w must be {n} contiguous fp32 values")
+    if scratch is None:
+        scratch = unified_loss_scratch(n, dev)
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    aux = torch.empty(8 + nc, dtype=torch.float32, device=dev)
+    dl = torch.empty_like(logits) if want_grad else None
+    rc = _lib.lib().mrirt_unified_loss(_ptr(logits), _ptr(labels), _ptr(boundary_w), n, nc, C.byref(cfg), _ptr(loss), _ptr(aux), _ptr(dl),
+                                       _ptr(scratch), scratch.numel(), _stream_ptr(None))
+    _lib.check(rc, "mrirt_unified_loss")
+    return loss.reshape(()), _unified_aux(aux), dl
+
+
 def make_inject_loss_and_grad(num_classes: int, class_weights, dice_weight: float, coord_layers=(1, 2, 3), mod_layers=(2,),
-                              ext: Optional[_lib.InrLossExt] = None):
+                              ext: Optional[Any] = None):
     """``jax.value_and_grad(loss_fn, has_aux=True)`` for the coordinate-injection network with the library's loss: returns
     ``fn(params, coords, mods, labels, dropout=None) -> ((loss, aux), grads)``; ``loss`` a 0-d device tensor, ``aux =
     {"ce_per_class", "dice_per_class"}`` and ``grads`` device tensors in ``params``' structure (``{"fourier": {"B"}, "mlp":
     [{"W", "b"}]}``).  One ``mrirt_inject_forward_train``, ``mrirt_inr_loss`` (``mrirt_inr_loss_ext`` with ``ext``, which adds
-    ``aux["terms"]``) and one ``mrirt_inject_backward``; nothing synchronises with the host."""
+    ``aux["terms"]``) and one ``mrirt_inject_backward``; nothing synchronises with the host.  When ``ext`` is a
+    ``MrirtUnifiedLoss`` (``unified_loss(...)``) the loss is the notebook's own, ``mrirt_unified_loss``: ``class_weights`` /
+    ``dice_weight`` are then not read, ``fn`` takes one more argument ``boundary_weights`` ((n,) fp32 or None: no boundary
+    term) and ``aux`` carries the keys of the notebook's ``loss_fn`` (``unified_loss_and_dlogits``)."""
+    unified = ext if isinstance(ext, _lib.UnifiedLoss) else None
     cw = [float(v) for v in np.asarray(class_weights, dtype=np.float32).reshape(-1)]
     if len(cw) != int(num_classes):
         raise ValueError(f"class_weights holds {len(cw)} values for {num_classes} classes")
+
+    def unified_loss_and_grad(params, coords, mods, labels, dropout=None, boundary_weights=None):
+        dev = _require_gpu()
+        desc = inject_desc(params, coord_layers, mod_layers)
+        if desc.width[desc.numLayers - 1] != int(num_classes):
+            raise ValueError(f"the network has {desc.width[desc.numLayers - 1]} outputs for {num_classes} classes")
+        c, m = _inject_points(coords, mods, dev, desc.numMods)
+        n = int(c.shape[0])
+        B, w, b = _inject_flat(params, dev)
+        lab = torch.as_tensor(labels).to(dev).to(torch.int32).contiguous()
+        bw = torch.as_tensor(boundary_weights).to(dev).to(torch.float32).contiguous() if boundary_weights is not None else None
+        scratch = inject_train_scratch(desc, n, dev)
+        logits = inject_forward_train(desc, B, w, b, c, m, n, scratch, dropout)
+        loss, aux, dl = unified_loss_and_dlogits(logits, lab, unified, bw)
+        gB, gw, gb = inject_backward(desc, B, w, c, m, n, dl, scratch, dropout)
+        return (loss, aux), _inject_split(desc, gB, gw, gb)
+
+    if unified is not None:
+        return unified_loss_and_grad
 
     def loss_and_grad(params, coords, mods, labels, dropout=None):
         dev = _require_gpu()
@@ -1726,8 +1827,15 @@ def train_inject(config: Dict[str, Any], cases_or_cache, params=None, log=None, 
     ``mrirt_inject_forward_train`` (dropout at keep ``1 - DROPOUT_RATE`` only for ``t > WARMUP_STEPS``, as cell 12 has it, with
     ``sample0 = g`` and ``index0 = 0``), the loss, ``mrirt_inject_backward`` accumulating after the first -- and one
     ``mrirt_inr_adamw_step`` over the flat parameters ``[w | B]`` and ``b`` with ``gscale = 1 / ACCUM_STEPS``, ``clipNorm =
-    CLIP_NORM`` and the rate of ``two_stage_schedule`` at ``t``.  The notebook's unified loss, hybrid sampler and coordinate
-    noise are not part of it.  ``save_path``: a directory; ``model_final.npz`` (the notebook's layout) is written there.
+    CLIP_NORM`` and the rate of ``two_stage_schedule`` at ``t``.  A config that holds UNIFIED_FOCAL_GAMMA trains with the
+    notebook's own loss (cell 8) instead, ``mrirt_unified_loss``: gamma and UNIFIED_FOCAL_LAMBDA (0.5 when absent), the Dice over
+    CLASS_WEIGHTS, BOUNDARY_WEIGHT (0.1 when absent) on the boundary weights ``cache.sample_field`` returns for the micro-batch's
+    own ``(RNG_SEED, g, n_tumour)`` (``cache.set_boundary()`` is called when the cache has no maps yet), and the TV weight of
+    cell 12: TV_WEIGHT_STAGE1 for ``t < STAGE1_STEPS``, else TV_WEIGHT_STAGE2; DICE_WEIGHT and the ``loss_ext_of_config`` loss
+    keys are then not read (TUMOR_RATIO still is), and ``log`` also gets ``train/ufl``, ``train/dice_loss``, ``train/tv_loss`` and
+    ``train/boundary_loss``, each the mean over the step's micro-batches.  A config without that key runs exactly as before.  The
+    notebook's hybrid, uncertainty-guided sampler and its coordinate noise are not part of it.  ``save_path``: a directory;
+    ``model_final.npz`` (the notebook's layout) is written there.
     Returns ``(params, state)``: NumPy ``params`` and a dict with ``loss_history`` and ``opt`` (the ``AdamWState`` over
     ``[w | B]`` and ``b``)."""
     nc, seed = int(config["NUM_CLASSES"]), int(config["RNG_SEED"])
@@ -1739,7 +1847,7 @@ def train_inject(config: Dict[str, Any], cases_or_cache, params=None, log=None, 
     schedule = two_stage_schedule(config["STAGE1_STEPS"], config["STAGE2_STEPS"], config["LR_STAGE1"], config["LR_STAGE2"], warmup, config["MIN_LR"])
     keep = float(np.float32(1.0) - np.float32(config["DROPOUT_RATE"]))
     ext_keys = _ext_keys_of(config)
-    ext = loss_ext_of_config(config, nc) if ext_keys else None
+    ext = loss_ext_of_config(config, nc) if ext_keys and "UNIFIED_FOCAL_GAMMA" not in config else None
     cache = cases_or_cache if isinstance(cases_or_cache, VoxelCache) else VoxelCache(cases_or_cache)
     n_tumour = n_tumour_of(micro, config.get("TUMOR_RATIO", 0.0)) if ext_keys else 0
     dev = cache.device
@@ -1757,6 +1865,8 @@ def train_inject(config: Dict[str, Any], cases_or_cache, params=None, log=None, 
     scratch = inject_train_scratch(desc, micro, dev)
     cw = [float(v) for v in config["CLASS_WEIGHTS"]]
     loss_history: List[Any] = []
+    if "UNIFIED_FOCAL_GAMMA" in config:
+        return _train_inject_unified(config, cache, desc, st, wB, b, nw, gwB, gb, scratch, schedule, keep, n_tumour, log, save_path)
     for t in range(total):
         losses = []
         for k in range(accum):
@@ -1772,6 +1882,11 @@ def train_inject(config: Dict[str, Any], cases_or_cache, params=None, log=None, 
         loss_history.append(torch.stack(losses).mean())      # stays on the device: without a log nothing waits for a step
         if log is not None:
             log(t + 1, {"train/loss": float(loss_history[-1]), "train/step": t + 1, "train/lr": schedule(t)})
+    return _train_inject_finish(desc, st, wB, b, nw, cache, loss_history, save_path)
+
+
+def _train_inject_finish(desc, st, wB, b, nw, cache, loss_history, save_path):
+    """What ``train_inject`` returns and writes, from the flat state of either of its loops."""
     loss_history = [float(v) for v in torch.stack(loss_history).cpu()]
     out = _inject_split(desc, wB[nw:].clone(), wB[:nw].clone(), b.clone())
     out = {"fourier": {"B": _inject_np(out["fourier"]["B"])}, "mlp": [{"W": _inject_np(p["W"]), "b": _inject_np(p["b"])} for p in out["mlp"]]}
@@ -1780,3 +1895,45 @@ def train_inject(config: Dict[str, Any], cases_or_cache, params=None, log=None, 
         save_path.mkdir(parents=True, exist_ok=True)
         inject_save(save_path / "model_final.npz", out)
     return out, {"params": out, "train_cache": cache, "loss_history": loss_history, "opt": st, "save_path": save_path}
+
+
+UNIFIED_LOG_KEYS = ("ufl", "dice_loss", "tv_loss", "boundary_loss")
+
+
+def _train_inject_unified(config, cache, desc, st, wB, b, nw, gwB, gb, scratch, schedule, keep, n_tumour, log, save_path):
+    """``train_inject``'s loop with the notebook's loss (cells 8 and 12): the same sampler, forward, backward and optimiser calls
+    with ``mrirt_unified_loss`` between forward and backward, on a scratch of its own."""
+    nc, seed = int(config["NUM_CLASSES"]), int(config["RNG_SEED"])
+    micro, accum = int(config["MICRO_BATCH_SIZE"]), int(config["ACCUM_STEPS"])
+    warmup, stage1 = int(config["WARMUP_STEPS"]), int(config["STAGE1_STEPS"])
+    total = stage1 + int(config["STAGE2_STEPS"])
+    cw = list(config["CLASS_WEIGHTS"])
+    if len(cw) != nc:
+        raise ValueError(f"CLASS_WEIGHTS holds {len(cw)} values for {nc} classes")
+    stages = [unified_loss(cw, float(config["UNIFIED_FOCAL_GAMMA"]), float(config.get("UNIFIED_FOCAL_LAMBDA", 0.5)), tv_weight=float(config[key]),
+                           boundary_weight=float(config.get("BOUNDARY_WEIGHT", 0.1))) for key in ("TV_WEIGHT_STAGE1", "TV_WEIGHT_STAGE2")]
+    if getattr(cache, "boundary_table", None) is None:
+        cache.set_boundary()
+    loss_scratch = unified_loss_scratch(micro, cache.device)
+    loss_history: List[Any] = []
+    for t in range(total):
+        cfg = stages[0] if t < stage1 else stages[1]
+        losses, terms = [], []
+        for k in range(accum):
+            g = t * accum + k
+            c, m, lab = cache.sample(seed, g, micro, n_tumour)
+            bw = cache.sample_field(seed, g, micro, n_tumour)
+            drop = inject_dropout(seed, keep, 1, g, 0) if t > warmup else None
+            m = m if desc.numMods else None
+            logits = inject_forward_train(desc, wB[nw:], wB[:nw], b, c, m, micro, scratch, drop)
+            loss, aux, dl = unified_loss_and_dlogits(logits, lab, cfg, bw, loss_scratch)
+            inject_backward(desc, wB[nw:], wB[:nw], c, m, micro, dl, scratch, drop, gwB[nw:], gwB[:nw], gb, accumulate=k > 0)
+            losses.append(loss)
+            terms.append(torch.stack([aux[key] for key in UNIFIED_LOG_KEYS]))
+        adamw_step(st, gwB, gb, schedule(t), 1.0 / accum, float(config["CLIP_NORM"]), weight_decay=float(config["WEIGHT_DECAY"]))
+        loss_history.append(torch.stack(losses).mean())
+        if log is not None:
+            mean = [float(v) for v in torch.stack(terms).mean(0).cpu()]
+            log(t + 1, {"train/loss": float(loss_history[-1]), "train/step": t + 1, "train/lr": schedule(t),
+                        **{"train/" + key: v for key, v in zip(UNIFIED_LOG_KEYS, mean)}})
+    return _train_inject_finish(desc, st, wB, b, nw, cache, loss_history, save_path)
