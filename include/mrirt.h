@@ -54,7 +54,10 @@ extern "C" {
  *    mrirt_boundary_weights;
  *    its training step (no new struct): mrirt_inject_train_scratch_bytes, mrirt_inject_forward_train, mrirt_inject_backward;
  *    the notebook's unified loss and the samplers' field gather: MrirtUnifiedLoss (mrirt_sizeof(20)),
- *    mrirt_unified_loss_scratch_bytes, mrirt_unified_loss, mrirt_inr_sample_field. */
+ *    mrirt_unified_loss_scratch_bytes, mrirt_unified_loss, mrirt_inr_sample_field;
+ *    the notebook's hybrid sampler and coordinate noise: MrirtInrClassIndex, MrirtInrHybrid (mrirt_sizeof(22), (23)),
+ *    mrirt_inr_class_count, mrirt_inr_class_index_scratch_bytes, mrirt_inr_class_index, mrirt_select_largest,
+ *    mrirt_inr_normal3, mrirt_inr_sample_candidates, mrirt_inr_sample_batch_hybrid. */
 #define MRIRT_ABI_VERSION 4
 
 typedef enum MrirtStatus {
@@ -1171,6 +1174,74 @@ int mrirt_unified_loss(const float* logits, const int32_t* labels, const float* 
 int mrirt_inr_sample_field(const MrirtInrCache* cache, const MrirtInrTumourIndex* tumour, const float* const* fields, uint64_t seed,
                            uint64_t batch_index, int64_t n, int64_t n_tumour, float* out, void* stream);
 
+/* The hybrid, uncertainty-guided sampler of the reference's notebooks/improved.ipynb (cell 9) and the coordinate noise of its
+ * cell 12.  Device pointers (the structs excepted), launches on `stream`, no host synchronisation, no allocation, integer
+ * atomics only, one writer per element: the same inputs give the same bits.  Every refusal happens before anything is launched,
+ * MRIRT_ERR_NULL before MRIRT_ERR_ARG.
+ *
+ * Class index (load time).  index holds the flat offset (x W + y) D + z of every voxel whose label lies in 0..C-1, ordered by
+ * class, then case, then ascending offset; offsets[k ncases + c] is the start of (class k, case c), offsets[C ncases] the
+ * length.  Labels outside the range are in no list.  mrirt_inr_class_count writes counts[c][k] (int64, [ncases][C]); the caller
+ * reads them once, forms the prefix sums in (class, case) order and sizes index.  mrirt_inr_class_index then fills index in
+ * three launches (the counts per chunk of 4096 voxels and class, their scan, the emit): no workgroup waits for another, there is
+ * no atomic append, and a slot outside its list's range is never written.  scratch: 16-byte aligned,
+ * mrirt_inr_class_index_scratch_bytes(cache, C) bytes (uint32 [ncases][ceil(H W D / 4096)][C], aligned to 256 bytes; 0 for a
+ * refused cache or C).  Refused: a NULL cache, counts, offsets, index or scratch (MRIRT_ERR_NULL); H W D >= 2^32, what
+ * mrirt_inr_sample_batch refuses of the cache, C outside 1..16, a scratch that is misaligned or too small. */
+typedef struct MrirtInrClassIndex {   /* mrirt_sizeof(22) */
+    const uint32_t* index;
+    const int64_t* offsets;           /* [numClasses * ncases + 1] */
+    uint32_t numClasses, reserved;
+} MrirtInrClassIndex;
+int mrirt_inr_class_count(const MrirtInrCache* cache, uint32_t num_classes, int64_t* counts, void* stream);
+int64_t mrirt_inr_class_index_scratch_bytes(const MrirtInrCache* cache, uint32_t num_classes);
+int mrirt_inr_class_index(const MrirtInrCache* cache, uint32_t num_classes, const int64_t* offsets, uint32_t* index, void* scratch,
+                          int64_t scratch_bytes, void* stream);
+/* Exact selection of the k largest of n values, 1 <= k <= n <= 65536 (else MRIRT_ERR_ARG; NULL values or out first).  The values
+ * are ordered by a 32-bit key that preserves their order: ~bits for a set sign bit, bits | 2^31 otherwise, so -0 lies below +0;
+ * every NaN takes the one key 2^32 - 1 above +inf, as NumPy sorts NaN last.  Among equal keys the higher index ranks higher.
+ * out is the k highest-ranking indices in ASCENDING INDEX order: sorted(np.argsort(key, kind="stable")[-k:]).  (The notebook's
+ * np.argsort is not stable, so its tie order is unspecified; it returns the picks in entropy order, which its later shuffle
+ * discards.)  One launch of one workgroup of 1024 threads, no global scratch: four radix passes over LDS histograms find the
+ * k-th key most significant byte first, a workgroup scan ranks the keys equal to it and places the picks. */
+int mrirt_select_largest(const float* values, int64_t n, int64_t k, uint32_t* out /* [k] */, void* stream);
+/* The unit normals of the coordinate noise.  Point i draws Philox4x32-10 under key `seed` at counter (i, batch lo, batch hi, 2),
+ * giving words r0..r3.  In fp64: u1 = (r0 + 1) 2^-32, u2 = r1 2^-32, R = sqrt(-2 log u1), z_x = R cos(2 pi u2), z_y = R sin(2 pi
+ * u2); from r2, r3 likewise z_z = R' cos(2 pi u2').  Each is rounded once to fp32.  out: [n][3].  One launch.  Refused: a NULL
+ * out; n outside 1..2^31-1. */
+int mrirt_inr_normal3(uint64_t seed, uint64_t batch_index, int64_t n, float* out, void* stream);
+/* The candidates the uncertainty is computed on: candidate j is mrirt_inr_sample_batch's draw at counter (j, batch lo, batch hi,
+ * 1) -- word 3 = 1 keeps the stream apart from the batch's own, which uses 0 -- written as mrirt_inr_sample_batch writes its
+ * rows (coords [n_cand][3], feats [n_cand][M], labels [n_cand]).  One launch.  Refusals: mrirt_inr_sample_batch's. */
+int mrirt_inr_sample_candidates(const MrirtInrCache* cache, uint64_t seed, uint64_t batch_index, int64_t n_cand, float* coords,
+                                float* feats, int32_t* labels, void* stream);
+/* One hybrid micro-batch, in one launch.  With U = nUncertain, P = nPerClass, C = classes->numClasses (0 when P == 0), row i is
+ *   i < U:            candidate picks[i] (any uint32 is a valid counter: a foreign picks cannot index outside a volume);
+ *   U <= i < U + C P: a voxel of class k = (i - U) / P.  With r0..r3 the words of mrirt_inr_sample_batch's point i and total_k =
+ *                     offsets[(k + 1) ncases] - offsets[k ncases] > 0: slot = offsets[k ncases] + floor(((r0 << 32) | r1) total_k
+ *                     / 2^64), the voxel is index[slot], its case the list that holds slot (a binary search over offsets):
+ *                     uniform over all class-k voxels of the cache, the distribution of the notebook's rejection loop, in one
+ *                     counter-based draw.  With total_k == 0 the uniform draw of the same words (the notebook pads instead);
+ *   otherwise:        mrirt_inr_sample_batch's row i, same bits.
+ * The batch is not shuffled, and the remainder of the notebook's n_balanced // C goes to the uniform rows instead of shrinking
+ * the batch.  labels, feats and field_out (fields[case][voxel], as mrirt_inr_sample_field) are those of the voxel.  Then, with
+ * noiseSigma > 0, coords[i][a] = c + noiseSigma * z_a(i) in fp32, product and sum each rounded, z = mrirt_inr_normal3's for
+ * (seed, batch_index, i); noiseSigma == 0 leaves the coordinates untouched.
+ * Refused: MRIRT_ERR_NULL for a NULL cache, hybrid, coords, labels, feats with modalities, exactly one of fields / field_out,
+ * picks with U > 0, classes or one of its pointers with P > 0; then what mrirt_inr_sample_batch refuses of the cache; then
+ * MRIRT_ERR_ARG for n outside 1..2^31-1, U or P outside 0..n, C outside 1..16 or classes->reserved != 0 with P > 0, U + C P > n,
+ * a noiseSigma that is negative or not finite, reserved != 0. */
+typedef struct MrirtInrHybrid {       /* mrirt_sizeof(23) */
+    int64_t nUncertain, nPerClass;
+    const uint32_t* picks;            /* device [nUncertain]; may be NULL when nUncertain == 0 */
+    float noiseSigma;                 /* >= 0, finite; 0: coordinates untouched */
+    uint32_t reserved;                /* 0 */
+} MrirtInrHybrid;
+int mrirt_inr_sample_batch_hybrid(const MrirtInrCache* cache, const MrirtInrClassIndex* classes /* may be NULL when nPerClass == 0 */,
+                                  const MrirtInrHybrid* hybrid, const float* const* fields /* or NULL */, uint64_t seed,
+                                  uint64_t batch_index, int64_t n, float* coords, float* feats, int32_t* labels,
+                                  float* field_out /* [n], required iff fields */, void* stream);
+
 /* ------------------------------------------------------------------------------------ */
 /* Misc                                                                                  */
 /* ------------------------------------------------------------------------------------ */
@@ -1180,8 +1251,8 @@ int mrirt_last_hip_error(void);            /* hipError_t of the last failed HIP 
 uint32_t mrirt_sizeof(uint32_t which);     /* 0 BratsParams, 1 RenderExt, 2 VolumeParams, 3 SdfParams, 4 InrDesc, 5 Skip,
                                               6 MeshParams, 7 InrCache, 8 AdamW, 9 InrTrainCfg, 10 InrTrainState,
                                               11 Muon, 13 InrLossExt, 14 InrTumourIndex, 15 InrTrainExt, 17 InjectDesc,
-                                              18 InjectDropout, 20 UnifiedLoss; 12, 16 and 19 are unassigned and stay
-                                              0, as every index beyond 20 */
+                                              18 InjectDropout, 20 UnifiedLoss, 22 InrClassIndex, 23 InrHybrid; 12, 16,
+                                              19 and 21 are unassigned and stay 0, as every index beyond 23 */
 /* Opt-in diagnostics (host only; the library installs nothing by itself): a SIGABRT handler that writes the native
  * backtrace of the aborting thread and, when file descriptor 2 has been redirected into a regular file (a test runner's
  * capture), the tail of that file to `fd` — a descriptor the caller duplicated before the redirection — and then chains

@@ -17,7 +17,7 @@ CSRC = PKG_DIR / "csrc"
 INCLUDE = PKG_DIR.parent / "include"
 SO_PATH = pathlib.Path(os.environ.get("MRIRT_LIB", PKG_DIR / "libmrirt.so"))   # override: A/B builds in development
 HIP_SOURCES = ["brats_march.hip", "brats_order.hip", "brats_skip.hip", "brats_c5.hip", "brats_slab.hip", "brats_ring.hip", "brats_backward.hip", "brats_soft.hip", "brats_tf.hip", "volume_march.hip", "grid_ops.hip", "inr_mlp.hip",
-               "inr_stream.hip", "inr_ws.hip", "inr_refine.hip", "inr_train.hip", "inr_optim.hip", "inr_muon.hip", "inr_lossx.hip", "inr_inject.hip", "inr_inject_train.hip", "inr_unified.hip", "mesh_rt.hip", "edt.hip", "surface.hip", "prep.hip", "components.hip", "abort_trace.cpp"]
+               "inr_stream.hip", "inr_ws.hip", "inr_refine.hip", "inr_train.hip", "inr_optim.hip", "inr_muon.hip", "inr_lossx.hip", "inr_inject.hip", "inr_inject_train.hip", "inr_unified.hip", "inr_hybrid.hip", "mesh_rt.hip", "edt.hip", "surface.hip", "prep.hip", "components.hip", "abort_trace.cpp"]
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17", "-Wall"]
 
 # every extern "C" symbol include/mrirt.h declares
@@ -50,6 +50,8 @@ ABI_SYMBOLS = [
     "mrirt_boundary_weights_scratch_bytes", "mrirt_boundary_weights",
     "mrirt_inject_train_scratch_bytes", "mrirt_inject_forward_train", "mrirt_inject_backward",
     "mrirt_unified_loss_scratch_bytes", "mrirt_unified_loss", "mrirt_inr_sample_field",
+    "mrirt_inr_class_count", "mrirt_inr_class_index_scratch_bytes", "mrirt_inr_class_index", "mrirt_select_largest",
+    "mrirt_inr_normal3", "mrirt_inr_sample_candidates", "mrirt_inr_sample_batch_hybrid",
 ]
 
 ABI_VERSION = 4          # MRIRT_ABI_VERSION of include/mrirt.h this binding was written against
@@ -189,6 +191,16 @@ class UnifiedLoss(C.Structure):
     """MrirtUnifiedLoss: the loss of notebooks/improved.ipynb, cell 8."""
     _fields_ = [("classWeights", f32 * 16), ("gamma", f32), ("lambda_", f32), ("tverskyAlpha", f32), ("tverskyBeta", f32),
                 ("uflWeight", f32), ("diceWeight", f32), ("tvWeight", f32), ("boundaryWeight", f32), ("flags", u32)]
+
+
+class InrClassIndex(C.Structure):
+    """MrirtInrClassIndex: device pointers to the voxel offsets by (class, case) and to the starts of those lists."""
+    _fields_ = [("index", C.c_void_p), ("offsets", C.c_void_p), ("numClasses", u32), ("reserved", u32)]
+
+
+class InrHybrid(C.Structure):
+    """MrirtInrHybrid: the segments of one hybrid micro-batch and the sigma of its coordinate noise."""
+    _fields_ = [("nUncertain", C.c_int64), ("nPerClass", C.c_int64), ("picks", C.c_void_p), ("noiseSigma", f32), ("reserved", u32)]
 
 
 class Skip(C.Structure):
@@ -525,6 +537,21 @@ def lib() -> C.CDLL:
     l.mrirt_unified_loss.restype = i32
     l.mrirt_inr_sample_field.argtypes = [C.POINTER(InrCache), C.POINTER(InrTumourIndex), vp, u64, u64, i64, i64, vp, vp]
     l.mrirt_inr_sample_field.restype = i32
+    l.mrirt_inr_class_count.argtypes = [C.POINTER(InrCache), u32, vp, vp]
+    l.mrirt_inr_class_count.restype = i32
+    l.mrirt_inr_class_index_scratch_bytes.argtypes = [C.POINTER(InrCache), u32]
+    l.mrirt_inr_class_index_scratch_bytes.restype = i64
+    l.mrirt_inr_class_index.argtypes = [C.POINTER(InrCache), u32, vp, vp, vp, i64, vp]
+    l.mrirt_inr_class_index.restype = i32
+    l.mrirt_select_largest.argtypes = [vp, i64, i64, vp, vp]
+    l.mrirt_select_largest.restype = i32
+    l.mrirt_inr_normal3.argtypes = [u64, u64, i64, vp, vp]
+    l.mrirt_inr_normal3.restype = i32
+    l.mrirt_inr_sample_candidates.argtypes = [C.POINTER(InrCache), u64, u64, i64, vp, vp, vp, vp]
+    l.mrirt_inr_sample_candidates.restype = i32
+    l.mrirt_inr_sample_batch_hybrid.argtypes = [C.POINTER(InrCache), C.POINTER(InrClassIndex), C.POINTER(InrHybrid), vp, u64, u64, i64, vp, vp, vp,
+                                                vp, vp]
+    l.mrirt_inr_sample_batch_hybrid.restype = i32
     l.mrirt_status_string.argtypes = [i32]
     l.mrirt_status_string.restype = C.c_char_p
     l.mrirt_sizeof.argtypes = [u32]
@@ -541,7 +568,7 @@ def lib() -> C.CDLL:
                                 InrTrainState, Muon, None, InrLossExt, InrTumourIndex, InrTrainExt)):          # index 12 is unassigned
         if st is not None and l.mrirt_sizeof(which) != C.sizeof(st):
             raise ImportError(f"ABI mismatch: {st.__name__} is {C.sizeof(st)} B here, {l.mrirt_sizeof(which)} B in {SO_PATH}")
-    for which, st in ((17, InjectDesc), (18, InjectDropout), (20, UnifiedLoss)):                           # 16 and 19 are unassigned
+    for which, st in ((17, InjectDesc), (18, InjectDropout), (20, UnifiedLoss), (22, InrClassIndex), (23, InrHybrid)):   # 16, 19 and 21 are unassigned
         if l.mrirt_sizeof(which) != C.sizeof(st):
             raise ImportError(f"ABI mismatch: {st.__name__} is {C.sizeof(st)} B here, {l.mrirt_sizeof(which)} B in {SO_PATH}")
     _LIB = l

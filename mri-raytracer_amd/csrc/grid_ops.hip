@@ -457,6 +457,8 @@ extern "C" uint32_t mrirt_sizeof(uint32_t which) {
         case 17: return (uint32_t)sizeof(MrirtInjectDesc);          // 16 stays unassigned too
         case 18: return (uint32_t)sizeof(MrirtInjectDropout);
         case 20: return (uint32_t)sizeof(MrirtUnifiedLoss);         // 19 stays unassigned too
+        case 22: return (uint32_t)sizeof(MrirtInrClassIndex);       // 21 stays unassigned too: callers were told it is 0
+        case 23: return (uint32_t)sizeof(MrirtInrHybrid);
         default: return 0;
     }
 }

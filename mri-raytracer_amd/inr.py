@@ -791,6 +791,7 @@ class VoxelCache:
         c.hwd[0], c.hwd[1], c.hwd[2] = shape
         self.desc = c
         self._tumour = None
+        self._classes: Dict[int, Any] = {}
 
     def tumour_index(self) -> _lib.InrTumourIndex:
         """``MrirtInrTumourIndex`` of the cache: the flat offsets of every case's voxels with seg > 0, ascending, built on the
@@ -858,6 +859,85 @@ class VoxelCache:
                                                int(batch_index) & (2 ** 64 - 1), int(n), int(n_tumour), _ptr(out), _stream_ptr(None))
         _lib.check(rc, "mrirt_inr_sample_field")
         return out
+
+    def class_index(self, num_classes: int) -> _lib.InrClassIndex:
+        """``MrirtInrClassIndex`` of the cache for ``num_classes`` classes: the flat offsets of the voxels with a label in
+        ``0 .. num_classes - 1``, by class, then case, then ascending, built on the first call for that ``num_classes`` by
+        ``mrirt_inr_class_count`` (one read of the (case, class) counts: load time) and ``mrirt_inr_class_index``, and kept
+        alive with the cache (``class_offsets[C]`` int64 (C ncases + 1,), ``class_voxels[C]`` a uint32 array viewed as int32)."""
+        nc = int(num_classes)
+        if nc not in self._classes:
+            lib, dev = _lib.lib(), self.device
+            nbytes = int(lib.mrirt_inr_class_index_scratch_bytes(C.byref(self.desc), nc))
+            if nbytes <= 0:
+                raise ValueError("class_index: num_classes must be 1..16 and the volume smaller than 2^32 voxels")
+            counts = torch.empty((self.n_cases, nc), dtype=torch.int64, device=dev)
+            _lib.check(lib.mrirt_inr_class_count(C.byref(self.desc), nc, _ptr(counts), _stream_ptr(None)), "mrirt_inr_class_count")
+            offsets = torch.zeros(nc * self.n_cases + 1, dtype=torch.int64)
+            offsets[1:] = torch.cumsum(counts.cpu().T.reshape(-1), 0)           # (class, case) order
+            d_offsets = offsets.to(dev)
+            voxels = torch.empty(max(int(offsets[-1]), 1), dtype=torch.int32, device=dev)
+            scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            _lib.check(lib.mrirt_inr_class_index(C.byref(self.desc), nc, _ptr(d_offsets), _ptr(voxels), _ptr(scratch), nbytes, _stream_ptr(None)),
+                       "mrirt_inr_class_index")
+            torch.cuda.current_stream(dev).synchronize()          # the scratch dies here
+            self._classes[nc] = (_lib.InrClassIndex(voxels.data_ptr(), d_offsets.data_ptr(), nc, 0), d_offsets, voxels)
+        return self._classes[nc][0]
+
+    @property
+    def class_offsets(self) -> Dict[int, torch.Tensor]:
+        return {k: v[1] for k, v in self._classes.items()}
+
+    @property
+    def class_voxels(self) -> Dict[int, torch.Tensor]:
+        return {k: v[2] for k, v in self._classes.items()}
+
+    def _rows(self, n: int):
+        dev = self.device
+        return (torch.empty((int(n), 3), dtype=torch.float32, device=dev), torch.empty((int(n), self.n_modalities), dtype=torch.float32, device=dev),
+                torch.empty(int(n), dtype=torch.int32, device=dev))
+
+    def sample_candidates(self, seed: int, batch_index: int, n_cand: int):
+        """``mrirt_inr_sample_candidates``: the ``n_cand`` candidate voxels of micro-batch ``batch_index`` (the sampler's draw at
+        counter word 3 = 1) as ``sample`` returns a batch: (coords, intensities, labels) on the device."""
+        coords, feats, labels = self._rows(n_cand)
+        rc = _lib.lib().mrirt_inr_sample_candidates(C.byref(self.desc), int(seed) & (2 ** 64 - 1), int(batch_index) & (2 ** 64 - 1), int(n_cand),
+                                                    _ptr(coords), _ptr(feats) if self.n_modalities else None, _ptr(labels), _stream_ptr(None))
+        _lib.check(rc, "mrirt_inr_sample_candidates")
+        return coords, feats, labels
+
+    def sample_hybrid(self, seed: int, batch_index: int, n: int, n_uncertain: int = 0, picks=None, n_per_class: int = 0, num_classes: int = 4,
+                      noise_sigma: float = 0.0, with_field: bool = False):
+        """``mrirt_inr_sample_batch_hybrid``: micro-batch ``batch_index`` with its first ``n_uncertain`` rows the candidates
+        ``picks`` (uint32 indices into ``sample_candidates``' stream: a device int32 tensor holding those bits, as
+        ``select_largest`` returns, or anything NumPy reads as uint32), then ``n_per_class`` voxels of each of ``num_classes``
+        classes from ``class_index(num_classes)``, then the rows of ``sample``; ``noise_sigma > 0`` adds ``noise_sigma *
+        normal3(seed, batch_index, n)`` to the coordinates.  Returns (coords, intensities, labels), and with ``with_field`` also
+        the boundary map's values (n,) at the rows' voxels (``set_boundary`` must have been called)."""
+        dev = self.device
+        hy = _lib.InrHybrid()
+        hy.nUncertain, hy.nPerClass, hy.noiseSigma, hy.reserved = int(n_uncertain), int(n_per_class), float(noise_sigma), 0
+        if int(n_uncertain) > 0:
+            if picks is None:
+                raise ValueError("sample_hybrid: n_uncertain > 0 needs picks")
+            if not isinstance(picks, torch.Tensor):
+                picks = torch.from_numpy(np.ascontiguousarray(np.asarray(picks).astype(np.uint32)).view(np.int32))
+            picks = picks.to(dev).contiguous()
+            if picks.dtype != torch.int32 or picks.numel() < int(n_uncertain):
+                raise ValueError(f"sample_hybrid: picks must hold {n_uncertain} 32-bit indices")
+            hy.picks = picks.data_ptr()
+        classes = C.byref(self.class_index(num_classes)) if int(n_per_class) > 0 else None
+        field = None
+        if with_field:
+            if getattr(self, "boundary_table", None) is None:
+                raise ValueError("sample_hybrid: call set_boundary() first")
+            field = torch.empty(int(n), dtype=torch.float32, device=dev)
+        coords, feats, labels = self._rows(n)
+        rc = _lib.lib().mrirt_inr_sample_batch_hybrid(C.byref(self.desc), classes, C.byref(hy), _ptr(self.boundary_table) if with_field else None,
+                                                      int(seed) & (2 ** 64 - 1), int(batch_index) & (2 ** 64 - 1), int(n), _ptr(coords),
+                                                      _ptr(feats) if self.n_modalities else None, _ptr(labels), _ptr(field), _stream_ptr(None))
+        _lib.check(rc, "mrirt_inr_sample_batch_hybrid")
+        return (coords, feats, labels, field) if with_field else (coords, feats, labels)
 
     def sample_voxels(self, case_indices, h_coords, w_coords, d_coords):
         """dataloader.py:86-96: (intensities (N, M) fp32, labels (N,) int16) of the given voxels, by plain indexing."""
@@ -1788,6 +1868,121 @@ def inject_autograd(B, Ws, bs, coords, mods, coord_layers=(1, 2, 3), mod_layers=
     return _InjectStep.apply(c, m, tuple(coord_layers), tuple(mod_layers), dropout, len(Ws), B, *Ws, *bs)
 
 
+# the notebook's hybrid sampler and coordinate noise (csrc/inr_hybrid.hip)
+
+def select_largest(values: torch.Tensor, k: int) -> torch.Tensor:
+    """``mrirt_select_largest``: the indices of the ``k`` largest of the fp32 device values (n <= 65536), in ascending index
+    order, as a device int32 tensor (k,): ``sorted(np.argsort(key, kind="stable")[-k:])`` under the order that puts -0 below +0
+    and every NaN last; among equals the higher index wins."""
+    v = values.reshape(-1)
+    if not v.is_cuda or v.dtype != torch.float32 or not v.is_contiguous():
+        raise ValueError("select_largest needs a contiguous fp32 device tensor")
+    out = torch.empty(max(int(k), 0), dtype=torch.int32, device=v.device)
+    _lib.check(_lib.lib().mrirt_select_largest(_ptr(v), int(v.numel()), int(k), _ptr(out), _stream_ptr(None)), "mrirt_select_largest")
+    return out
+
+
+def normal3(seed: int, batch_index: int, n: int) -> torch.Tensor:
+    """``mrirt_inr_normal3``: the (n, 3) fp32 unit normals the hybrid sampler scales by its sigma for ``(seed, batch_index)``."""
+    out = torch.empty((int(n), 3), dtype=torch.float32, device=_require_gpu())
+    _lib.check(_lib.lib().mrirt_inr_normal3(int(seed) & (2 ** 64 - 1), int(batch_index) & (2 ** 64 - 1), int(n), _ptr(out), _stream_ptr(None)),
+               "mrirt_inr_normal3")
+    return out
+
+
+def hybrid_counts(micro: int, uncertainty_ratio: float, balanced_ratio: float, num_classes: int, use_uncertainty: bool,
+                  max_candidates: int = 10000) -> Tuple[int, int, int]:
+    """``(n_uncertain, n_per_class, n_cand)`` of the notebook's ``sample_batch_hybrid`` (cell 9), with its truncations:
+    ``int(micro * uncertainty_ratio)`` (0 without uncertainty), ``int(micro * balanced_ratio) // num_classes`` and
+    ``min(max_candidates, 10 * n_uncertain)``."""
+    n_unc = int(int(micro) * float(uncertainty_ratio)) if use_uncertainty else 0
+    n_per = int(int(micro) * float(balanced_ratio)) // int(num_classes)
+    return n_unc, n_per, min(int(max_candidates), 10 * n_unc)
+
+
+def inject_uncertainty(desc: _lib.InjectDesc, B: torch.Tensor, w_flat: torch.Tensor, b_flat: torch.Tensor, coords: torch.Tensor, mods, n: int,
+                       dropout: _lib.InjectDropout, scratch=None) -> torch.Tensor:
+    """``mrirt_inject_uncertainty`` on flat parameters: the MC-dropout entropy (n,) fp32 of ``dropout.samples`` passes.
+    ``scratch``: what ``_inject_scratch(desc, n', dev)`` returned for some ``n' >= n``, allocated when None."""
+    ent = torch.empty(int(n), dtype=torch.float32, device=w_flat.device)
+    scratch, nbytes = scratch if scratch is not None else _inject_scratch(desc, int(n), w_flat.device)
+    rc = _lib.lib().mrirt_inject_uncertainty(C.byref(desc), _ptr(B), _ptr(w_flat), _ptr(b_flat), _ptr(coords), _ptr(mods) if mods is not None else None,
+                                             int(n), C.byref(dropout), _ptr(ent), None, _ptr(scratch), nbytes, _stream_ptr(None))
+    _lib.check(rc, "mrirt_inject_uncertainty")
+    return ent
+
+
+HYBRID_KEYS = ("UNCERTAINTY_RATIO", "BALANCED_RATIO")
+NOISE_KEYS = ("COORD_NOISE_SIGMA_INIT", "COORD_NOISE_SIGMA_FINAL")
+
+
+class _HybridBatches:
+    """The micro-batches of ``train_inject`` under the notebook's hybrid keys and / or its noise keys (cells 9 and 12)."""
+
+    def __init__(self, config, cache: VoxelCache, desc: _lib.InjectDesc, keep: float, with_field: bool):
+        self.cache, self.desc, self.keep, self.with_field = cache, desc, keep, with_field
+        self.nc, self.seed, self.micro = int(config["NUM_CLASSES"]), int(config["RNG_SEED"]), int(config["MICRO_BATCH_SIZE"])
+        self.warmup, self.stage1 = int(config["WARMUP_STEPS"]), int(config["STAGE1_STEPS"])
+        self.total = self.stage1 + int(config["STAGE2_STEPS"])
+        self.hybrid = "UNCERTAINTY_RATIO" in config
+        self.ratios = (float(config.get("UNCERTAINTY_RATIO", 0.0)), float(config.get("UNCERTAINTY_RATIO_STAGE2", 0.75)))
+        self.balanced = float(config.get("BALANCED_RATIO", 0.0))
+        self.samples = int(config.get("UNCERTAINTY_MC_SAMPLES", 5))
+        self.sigmas = (float(config.get("COORD_NOISE_SIGMA_INIT", 0.0)), float(config.get("COORD_NOISE_SIGMA_FINAL", 0.0)))
+        self.scratch = None
+        if self.hybrid:
+            if not 1 <= self.samples < 2 ** 24:
+                raise ValueError("UNCERTAINTY_MC_SAMPLES must be 1 .. 2^24 - 1")
+            most = 0
+            for r in self.ratios:
+                U, P, n_cand = self.counts(r, True)
+                if U < 0 or P < 0 or U > self.micro or U > n_cand or n_cand > 65536:
+                    raise ValueError(f"an uncertainty ratio of {r} with BALANCED_RATIO {self.balanced} gives {U} + {self.nc} x {P} of {self.micro} "
+                                     f"points from {n_cand} candidates")
+                most = max(most, n_cand)
+            if most > 0:
+                self.scratch = _inject_scratch(desc, most, cache.device)
+
+    def counts(self, ratio: float, use_uncertainty: bool) -> Tuple[int, int, int]:
+        """``hybrid_counts`` with the balanced segment cut to what the uncertain one leaves: the notebook's stage-2 ratios
+        (0.75 + 0.3) let its batch grow past MICRO_BATCH_SIZE; here a micro-batch always has MICRO_BATCH_SIZE points."""
+        U, P, n_cand = hybrid_counts(self.micro, ratio, self.balanced, self.nc, use_uncertainty)
+        return U, min(P, max(self.micro - U, 0) // self.nc), n_cand
+
+    def sigma(self, t: int) -> float:
+        p = t / self.total
+        return float(np.float32(self.sigmas[0] * (1.0 - p) + self.sigmas[1] * p))
+
+    def __call__(self, t: int, g: int, B: torch.Tensor, w: torch.Tensor, b: torch.Tensor):
+        """(coords, mods, labels, boundary weights or None) of global micro-batch ``g`` in step ``t``, scored by the parameters given."""
+        U = P = 0
+        picks = None
+        if self.hybrid:
+            U, P, n_cand = self.counts(self.ratios[0] if t < self.stage1 else self.ratios[1], t > self.warmup)
+        if U > 0:
+            cc, cm, _ = self.cache.sample_candidates(self.seed, g, n_cand)
+            S = self.samples
+            dp = inject_dropout(self.seed + 1, self.keep, S, (g * S) % (2 ** 24 - S), 0)
+            ent = inject_uncertainty(self.desc, B, w, b, cc, cm if self.desc.numMods else None, n_cand, dp, self.scratch)
+            picks = select_largest(ent, U)
+        out = self.cache.sample_hybrid(self.seed, g, self.micro, U, picks, P, self.nc, self.sigma(t), self.with_field)
+        return out if self.with_field else (*out, None)
+
+
+def _hybrid_of_config(config) -> Tuple[bool, bool]:
+    """(hybrid keys present, noise keys present); refuses half a group and TUMOR_RATIO beside either."""
+    hybrid, noise = [k in config for k in HYBRID_KEYS], [k in config for k in NOISE_KEYS]
+    if any(hybrid) != all(hybrid) or any(noise) != all(noise):
+        raise ValueError("UNCERTAINTY_RATIO goes with BALANCED_RATIO, COORD_NOISE_SIGMA_INIT with COORD_NOISE_SIGMA_FINAL")
+    if (any(hybrid) or any(noise)) and "TUMOR_RATIO" in config:
+        raise ValueError("TUMOR_RATIO cannot be combined with the hybrid sampler's keys or the coordinate noise keys")
+    if any(noise):
+        for k in NOISE_KEYS:
+            if not (np.isfinite(float(config[k])) and float(config[k]) >= 0.0):
+                raise ValueError(f"{k} must be finite and >= 0")
+    return any(hybrid), any(noise)
+
+
 def two_stage_schedule(stage1_steps: int, stage2_steps: int, lr_stage1: float, lr_stage2: float, warmup_steps: int, min_lr: float):
     """The notebook's two-stage rate (cell 11) as ``schedule(step) -> float`` in host fp64: a linear warm-up to ``lr_stage1``,
     a linear blend to ``lr_stage2`` at ``stage1_steps``, then to ``min_lr`` over ``stage2_steps``.  With ``stage2_steps == 0``
@@ -1833,9 +2028,20 @@ def train_inject(config: Dict[str, Any], cases_or_cache, params=None, log=None, 
     own ``(RNG_SEED, g, n_tumour)`` (``cache.set_boundary()`` is called when the cache has no maps yet), and the TV weight of
     cell 12: TV_WEIGHT_STAGE1 for ``t < STAGE1_STEPS``, else TV_WEIGHT_STAGE2; DICE_WEIGHT and the ``loss_ext_of_config`` loss
     keys are then not read (TUMOR_RATIO still is), and ``log`` also gets ``train/ufl``, ``train/dice_loss``, ``train/tv_loss`` and
-    ``train/boundary_loss``, each the mean over the step's micro-batches.  A config without that key runs exactly as before.  The
-    notebook's hybrid, uncertainty-guided sampler and its coordinate noise are not part of it.  ``save_path``: a directory;
-    ``model_final.npz`` (the notebook's layout) is written there.
+    ``train/boundary_loss``, each the mean over the step's micro-batches.  A config without that key runs exactly as before.
+    UNCERTAINTY_RATIO with BALANCED_RATIO switches either loop to the notebook's hybrid sampler (cell 9; UNIFORM_RATIO is accepted
+    and not read, as there): with ``(U, P, n_cand) = hybrid_counts(MICRO_BATCH_SIZE, ratio, BALANCED_RATIO, NUM_CLASSES, t >
+    WARMUP_STEPS)`` and ``ratio`` UNCERTAINTY_RATIO for ``t < STAGE1_STEPS``, else UNCERTAINTY_RATIO_STAGE2 (0.75 when absent), a
+    micro-batch with ``U > 0`` draws ``cache.sample_candidates(RNG_SEED, g, n_cand)``, scores them with
+    ``mrirt_inject_uncertainty`` on the current parameters (``S`` = UNCERTAINTY_MC_SAMPLES, 5 when absent, passes at keep ``1 -
+    DROPOUT_RATE``, dropout seed ``RNG_SEED + 1``, ``sample0 = (g S) % (2^24 - S)``, ``index0 = 0``), keeps ``select_largest(entropy,
+    U)`` and trains on ``cache.sample_hybrid(RNG_SEED, g, MICRO_BATCH_SIZE, U, picks, P, NUM_CLASSES, sigma)``; where ``U + NUM_CLASSES
+    P`` would exceed the micro-batch (the notebook's stage 2: 0.75 + 0.3), ``P`` is cut to ``(MICRO_BATCH_SIZE - U) // NUM_CLASSES``.
+    COORD_NOISE_SIGMA_INIT with COORD_NOISE_SIGMA_FINAL, alone or beside the hybrid keys, add cell 12's coordinate noise: ``sigma =
+    INIT (1 - p) + FINAL p`` with ``p = t / (STAGE1_STEPS + STAGE2_STEPS)`` in double, passed as fp32.  With either group the
+    unified loop takes its boundary weights from the same launch (``with_field``) and does not call ``sample_field``; TUMOR_RATIO
+    beside either group raises ``ValueError`` before a cache is built.  A config without these keys runs exactly as before.
+    ``save_path``: a directory; ``model_final.npz`` (the notebook's layout) is written there.
     Returns ``(params, state)``: NumPy ``params`` and a dict with ``loss_history`` and ``opt`` (the ``AdamWState`` over
     ``[w | B]`` and ``b``)."""
     nc, seed = int(config["NUM_CLASSES"]), int(config["RNG_SEED"])
@@ -1847,6 +2053,7 @@ def train_inject(config: Dict[str, Any], cases_or_cache, params=None, log=None, 
     schedule = two_stage_schedule(config["STAGE1_STEPS"], config["STAGE2_STEPS"], config["LR_STAGE1"], config["LR_STAGE2"], warmup, config["MIN_LR"])
     keep = float(np.float32(1.0) - np.float32(config["DROPOUT_RATE"]))
     ext_keys = _ext_keys_of(config)
+    hybrid, noise = _hybrid_of_config(config)
     ext = loss_ext_of_config(config, nc) if ext_keys and "UNIFIED_FOCAL_GAMMA" not in config else None
     cache = cases_or_cache if isinstance(cases_or_cache, VoxelCache) else VoxelCache(cases_or_cache)
     n_tumour = n_tumour_of(micro, config.get("TUMOR_RATIO", 0.0)) if ext_keys else 0
@@ -1865,13 +2072,15 @@ def train_inject(config: Dict[str, Any], cases_or_cache, params=None, log=None, 
     scratch = inject_train_scratch(desc, micro, dev)
     cw = [float(v) for v in config["CLASS_WEIGHTS"]]
     loss_history: List[Any] = []
-    if "UNIFIED_FOCAL_GAMMA" in config:
-        return _train_inject_unified(config, cache, desc, st, wB, b, nw, gwB, gb, scratch, schedule, keep, n_tumour, log, save_path)
+    unified = "UNIFIED_FOCAL_GAMMA" in config
+    batches = _HybridBatches(config, cache, desc, keep, unified) if hybrid or noise else None
+    if unified:
+        return _train_inject_unified(config, cache, desc, st, wB, b, nw, gwB, gb, scratch, schedule, keep, n_tumour, log, save_path, batches)
     for t in range(total):
         losses = []
         for k in range(accum):
             g = t * accum + k
-            c, m, lab = cache.sample(seed, g, micro, n_tumour)
+            c, m, lab = cache.sample(seed, g, micro, n_tumour) if batches is None else batches(t, g, wB[nw:], wB[:nw], b)[:3]
             drop = inject_dropout(seed, keep, 1, g, 0) if t > warmup else None
             m = m if desc.numMods else None
             logits = inject_forward_train(desc, wB[nw:], wB[:nw], b, c, m, micro, scratch, drop)
@@ -1900,9 +2109,10 @@ def _train_inject_finish(desc, st, wB, b, nw, cache, loss_history, save_path):
 UNIFIED_LOG_KEYS = ("ufl", "dice_loss", "tv_loss", "boundary_loss")
 
 
-def _train_inject_unified(config, cache, desc, st, wB, b, nw, gwB, gb, scratch, schedule, keep, n_tumour, log, save_path):
+def _train_inject_unified(config, cache, desc, st, wB, b, nw, gwB, gb, scratch, schedule, keep, n_tumour, log, save_path, batches=None):
     """``train_inject``'s loop with the notebook's loss (cells 8 and 12): the same sampler, forward, backward and optimiser calls
-    with ``mrirt_unified_loss`` between forward and backward, on a scratch of its own."""
+    with ``mrirt_unified_loss`` between forward and backward, on a scratch of its own.  ``batches``: the hybrid sampler's, which
+    returns the boundary weights with the batch."""
     nc, seed = int(config["NUM_CLASSES"]), int(config["RNG_SEED"])
     micro, accum = int(config["MICRO_BATCH_SIZE"]), int(config["ACCUM_STEPS"])
     warmup, stage1 = int(config["WARMUP_STEPS"]), int(config["STAGE1_STEPS"])
@@ -1921,8 +2131,11 @@ def _train_inject_unified(config, cache, desc, st, wB, b, nw, gwB, gb, scratch, 
         losses, terms = [], []
         for k in range(accum):
             g = t * accum + k
-            c, m, lab = cache.sample(seed, g, micro, n_tumour)
-            bw = cache.sample_field(seed, g, micro, n_tumour)
+            if batches is None:
+                c, m, lab = cache.sample(seed, g, micro, n_tumour)
+                bw = cache.sample_field(seed, g, micro, n_tumour)
+            else:
+                c, m, lab, bw = batches(t, g, wB[nw:], wB[:nw], b)
             drop = inject_dropout(seed, keep, 1, g, 0) if t > warmup else None
             m = m if desc.numMods else None
             logits = inject_forward_train(desc, wB[nw:], wB[:nw], b, c, m, micro, scratch, drop)
