@@ -57,7 +57,9 @@ extern "C" {
  *    mrirt_unified_loss_scratch_bytes, mrirt_unified_loss, mrirt_inr_sample_field;
  *    the notebook's hybrid sampler and coordinate noise: MrirtInrClassIndex, MrirtInrHybrid (mrirt_sizeof(22), (23)),
  *    mrirt_inr_class_count, mrirt_inr_class_index_scratch_bytes, mrirt_inr_class_index, mrirt_select_largest,
- *    mrirt_inr_normal3, mrirt_inr_sample_candidates, mrirt_inr_sample_batch_hybrid. */
+ *    mrirt_inr_normal3, mrirt_inr_sample_candidates, mrirt_inr_sample_batch_hybrid;
+ *    the fused forward of the coordinate-injection INR and the C5 frame driven by it (no new struct):
+ *    mrirt_inject_fused_lds_bytes, mrirt_inject_classify, mrirt_render_brats_inject. */
 #define MRIRT_ABI_VERSION 4
 
 typedef enum MrirtStatus {
@@ -1241,6 +1243,42 @@ int mrirt_inr_sample_batch_hybrid(const MrirtInrCache* cache, const MrirtInrClas
                                   const MrirtInrHybrid* hybrid, const float* const* fields /* or NULL */, uint64_t seed,
                                   uint64_t batch_index, int64_t n, float* coords, float* feats, int32_t* labels,
                                   float* field_out /* [n], required iff fields */, void* stream);
+
+/* ------------------------------------------------------------------------------------ */
+/* Coordinate-injection INR: fused forward, and the per-sample render driven by it      */
+/* ------------------------------------------------------------------------------------ */
+/* Added within ABI 4: three symbols, no new struct.  csrc/inr_inject_fused.hip, csrc/brats_c5.hip; DESIGN.md section 27.
+ * The evaluation forward of the section "Coordinate-injection INR" above as ONE launch: a workgroup keeps the whole network
+ * in LDS (every W_l with its input padded to 4 and its output to 16, the biases, B) and each of its waves carries 16 rows
+ * from coordinates to class without touching global memory in between.  Features, the order of every layer's products
+ * (v_mfma_f32_16x16x4_f32 over k in increasing groups of four from +0, then + bias, then the ReLU) and the argmax are those of
+ * mrirt_inject_forward without dropout: logits and classes are the same bits.  No dropout, no scratch, no float atomics, one
+ * writer per output.
+ * mrirt_inject_fused_lds_bytes: the dynamic LDS the launch asks for, or 0 when the fused path refuses the shape -- a desc
+ *   mrirt_inject_forward refuses, or one whose layout exceeds 160 KiB (the notebook's shape takes 143,936 bytes; shapes with a
+ *   256-wide layer mostly do not fit).  A refused shape is never served another way.
+ * mrirt_inject_classify: coords [n_max][3], mods [n_max][numMods] (may be NULL when numMods == 0), count_dev NULL or a device
+ *   word: the call processes min(*count_dev, n_max) rows (n_max without count_dev), read by the kernel itself -- no host
+ *   synchronisation; rows at or beyond the count are neither read nor written.  argmax [n_max] int16 and logits [n_max][C]:
+ *   either may be NULL, not both.  Refused before any HIP call: MRIRT_ERR_NULL for a NULL desc, B, w, b, coords, mods (unless
+ *   numMods == 0) or both outputs; MRIRT_ERR_ARG for a desc mrirt_inject_forward refuses, a shape whose
+ *   mrirt_inject_fused_lds_bytes is 0, n_max outside 1 .. 2^31 - 1.
+ * mrirt_render_brats_inject: mrirt_render_brats_inr with this network: the same plan / emit / composite launches, the same
+ *   scratch of mrirt_brats_inr_scratch_bytes(params, chunk_steps) bytes, the same pass bound, the same three stats_dev
+ *   counters and the same refusals, each before anything touches the scratch; the classifier of a pass is the fused forward
+ *   over the pass's coordinates and its four z-scored modalities, the batch size read from the device.  Additionally refused:
+ *   MRIRT_ERR_NULL for a NULL desc, B, w or b; MRIRT_ERR_ARG for numMods != 4, a shape the fused path refuses, and
+ *   imageSize[0] imageSize[1] chunk_steps >= 2^31.  The frame is the same bits as marching with the class stream
+ *   mrirt_inject_forward gives for every sample (mrirt_brats_sample_counts, mrirt_brats_emit_samples,
+ *   mrirt_render_brats_stream). */
+int64_t mrirt_inject_fused_lds_bytes(const MrirtInjectDesc* desc);
+int mrirt_inject_classify(const MrirtInjectDesc* desc, const float* B, const float* w, const float* b, const float* coords,
+                          const float* mods, int64_t n_max, const uint32_t* count_dev, int16_t* argmax, float* logits,
+                          void* stream);
+int mrirt_render_brats_inject(const MrirtBratsParams* params, const MrirtRenderExt* ext, const void* const vol[4],
+                              const void* labels, const MrirtInjectDesc* desc, const float* B, const float* w, const float* b,
+                              const float zmu[4], const float zsigma[4], uint32_t chunk_steps, void* scratch,
+                              int64_t scratch_bytes, void* out_rgba, int64_t pitch_px, uint64_t* stats_dev, void* stream);
 
 /* ------------------------------------------------------------------------------------ */
 /* Misc                                                                                  */

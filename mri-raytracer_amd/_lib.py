@@ -17,7 +17,7 @@ CSRC = PKG_DIR / "csrc"
 INCLUDE = PKG_DIR.parent / "include"
 SO_PATH = pathlib.Path(os.environ.get("MRIRT_LIB", PKG_DIR / "libmrirt.so"))   # override: A/B builds in development
 HIP_SOURCES = ["brats_march.hip", "brats_order.hip", "brats_skip.hip", "brats_c5.hip", "brats_slab.hip", "brats_ring.hip", "brats_backward.hip", "brats_soft.hip", "brats_tf.hip", "volume_march.hip", "grid_ops.hip", "inr_mlp.hip",
-               "inr_stream.hip", "inr_ws.hip", "inr_refine.hip", "inr_train.hip", "inr_optim.hip", "inr_muon.hip", "inr_lossx.hip", "inr_inject.hip", "inr_inject_train.hip", "inr_unified.hip", "inr_hybrid.hip", "mesh_rt.hip", "edt.hip", "surface.hip", "prep.hip", "components.hip", "abort_trace.cpp"]
+               "inr_stream.hip", "inr_ws.hip", "inr_refine.hip", "inr_train.hip", "inr_optim.hip", "inr_muon.hip", "inr_lossx.hip", "inr_inject.hip", "inr_inject_fused.hip", "inr_inject_train.hip", "inr_unified.hip", "inr_hybrid.hip", "mesh_rt.hip", "edt.hip", "surface.hip", "prep.hip", "components.hip", "abort_trace.cpp"]
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17", "-Wall"]
 
 # every extern "C" symbol include/mrirt.h declares
@@ -52,6 +52,7 @@ ABI_SYMBOLS = [
     "mrirt_unified_loss_scratch_bytes", "mrirt_unified_loss", "mrirt_inr_sample_field",
     "mrirt_inr_class_count", "mrirt_inr_class_index_scratch_bytes", "mrirt_inr_class_index", "mrirt_select_largest",
     "mrirt_inr_normal3", "mrirt_inr_sample_candidates", "mrirt_inr_sample_batch_hybrid",
+    "mrirt_inject_fused_lds_bytes", "mrirt_inject_classify", "mrirt_render_brats_inject",
 ]
 
 ABI_VERSION = 4          # MRIRT_ABI_VERSION of include/mrirt.h this binding was written against
@@ -552,6 +553,13 @@ def lib() -> C.CDLL:
     l.mrirt_inr_sample_batch_hybrid.argtypes = [C.POINTER(InrCache), C.POINTER(InrClassIndex), C.POINTER(InrHybrid), vp, u64, u64, i64, vp, vp, vp,
                                                 vp, vp]
     l.mrirt_inr_sample_batch_hybrid.restype = i32
+    l.mrirt_inject_fused_lds_bytes.argtypes = [C.POINTER(InjectDesc)]
+    l.mrirt_inject_fused_lds_bytes.restype = i64
+    l.mrirt_inject_classify.argtypes = [*inj, vp, vp, i64, vp, vp, vp, vp]
+    l.mrirt_inject_classify.restype = i32
+    l.mrirt_render_brats_inject.argtypes = [C.POINTER(BratsParams), C.POINTER(RenderExt), C.POINTER(vp), vp, *inj,
+                                            C.POINTER(f32), C.POINTER(f32), u32, vp, i64, vp, i64, vp, vp]
+    l.mrirt_render_brats_inject.restype = i32
     l.mrirt_status_string.argtypes = [i32]
     l.mrirt_status_string.restype = C.c_char_p
     l.mrirt_sizeof.argtypes = [u32]

@@ -2,7 +2,7 @@
 // and composited with the class as the prediction overlay.  Build-defined extension.  Two forms:
 //   whole-ray: mrirt_brats_sample_counts + mrirt_brats_emit_samples write every sample's MLP inputs, the caller classifies
 //              them, and mrirt_render_brats_stream (brats_march.hip: the generic kernel) marches with the class stream;
-//   chunked:   mrirt_render_brats_inr, ERT-aware, `chunk` steps per pass (see "C5, chunked" below).
+//   chunked:   mrirt_render_brats_inr (and mrirt_render_brats_inject of inr_inject_fused.hip, on the same frame loop), ERT-aware, `chunk` steps per pass (see "C5, chunked" below).
 // The rays, the cell arithmetic, the gathers and the compositing step are the march's own (brats_device.h); prepare() is
 // brats_march.hip's (brats_host.h).
 #include "brats_host.h"
@@ -364,8 +364,6 @@ extern "C" int mrirt_brats_emit_samples(const MrirtBratsParams* p, const MrirtRe
 // ---------------------------------------------------------------------------------------
 namespace mrirt {
 
-constexpr uint32_t kC5MaxPasses = 1024;
-
 __global__ void c5_sum_kernel(const uint32_t* __restrict__ counters, uint32_t n, uint64_t* __restrict__ queries) {
     uint64_t s = 0;
     for (uint32_t i = threadIdx.x; i < n; i += 64) s += counters[i];
@@ -373,8 +371,6 @@ __global__ void c5_sum_kernel(const uint32_t* __restrict__ counters, uint32_t n,
     for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
     if (threadIdx.x == 0) atomicAdd(reinterpret_cast<unsigned long long*>(queries), (unsigned long long)s);
 }
-
-struct C5Scratch { uint32_t* counters; C5Ray* rays; float4* geom; uint2* rowOwner; float* coords; float* feats; float* mix; uint32_t* seg; int16_t* classes; int64_t cap, bytes; };
 
 static int64_t align256(int64_t x) { return (x + 255) & ~(int64_t)255; }
 
@@ -446,18 +442,22 @@ extern "C" int64_t mrirt_brats_inr_scratch_bytes(const MrirtBratsParams* p, uint
     return c5_carve(p, chunk_steps, nullptr, sc) == MRIRT_OK ? sc.bytes : 0;
 }
 
-extern "C" int mrirt_render_brats_inr(const MrirtBratsParams* p, const MrirtRenderExt* ext, const void* const vol[4],
-                                      const void* labels, const MrirtInrDesc* net, const float zmu[4], const float zsigma[4],
-                                      uint32_t chunk_steps, void* scratch, int64_t scratch_bytes,
-                                      void* out_rgba, int64_t pitch_px, uint64_t* stats_dev, void* stream) {
-    if (!out_rgba || !scratch || !net || !vol || !zmu || !zsigma) return MRIRT_ERR_NULL;
+namespace mrirt {
+
+// what both chunked entry points refuse of their common arguments before they look at their network
+int c5_check_common(const MrirtRenderExt* ext, const void* const vol[4], const float* zmu, const float* zsigma, const void* scratch,
+                    const void* out_rgba) {
+    if (!out_rgba || !scratch || !vol || !zmu || !zsigma) return MRIRT_ERR_NULL;
     const bool mod4 = ext && ext->layout == MRIRT_LAYOUT_MOD4;
     for (int m = 0; m < (mod4 ? 1 : 4); ++m) if (!vol[m]) return MRIRT_ERR_NULL;     // the MLP reads all four modalities
     if (ext && ext->tileSize != 0) return MRIRT_ERR_ARG;                      // whole-frame only
-    if ((net->kind != MRIRT_INR_FOURIER_RELU && net->kind != MRIRT_INR_SIREN) || net->numMods != 4) return MRIRT_ERR_ARG;
-    // what inr_forward_dev_n would refuse in the first pass, after the plan and the emission had written the scratch
-    if (mrirt_inr_pack_bytes(net) <= 0) return MRIRT_ERR_ARG;
-    if (!net->weights || !net->biases) return MRIRT_ERR_NULL;
+    return MRIRT_OK;
+}
+
+// The frame loop of the chunked C5 render (declared in brats_host.h)
+int c5_frame(const MrirtBratsParams* p, const MrirtRenderExt* ext, const void* const vol[4], const void* labels, const float zmu[4],
+             const float zsigma[4], uint32_t chunk_steps, void* scratch, int64_t scratch_bytes, void* out_rgba, int64_t pitch_px,
+             uint64_t* stats_dev, void* stream, int64_t maxCap, C5Classify classify, const void* ctx) {
     K1Args a;
     Prepared cfg;
     int rc = prepare(p, ext, vol, labels, nullptr, true, pitch_px, a, cfg);
@@ -469,6 +469,7 @@ extern "C" int mrirt_render_brats_inr(const MrirtBratsParams* p, const MrirtRend
     rc = c5_carve(p, chunk_steps, scratch, sc);
     if (rc != MRIRT_OK) return rc;
     if (scratch_bytes < sc.bytes) return MRIRT_ERR_ARG;
+    if (sc.cap > maxCap) return MRIRT_ERR_ARG;
     // passes: a ray's chord is at most the box diagonal; the march counts it with the running fp32 sum t += stepSize, whose
     // increments are each off by up to half an ulp of t — a relative drift of up to ulp(tFar) / (2 stepSize) over the chord
     // when stepSize is only a few tens of ulps of t.  The bound carries twice that drift (tFar = the farthest any
@@ -499,7 +500,7 @@ extern "C" int mrirt_render_brats_inr(const MrirtBratsParams* p, const MrirtRend
         rc = strict ? c5_launch_plan<true>(a, e, cfg.layout, cfg.shade, sc, c, chunk_steps, s)
                     : c5_launch_plan<false>(a, e, cfg.layout, cfg.shade, sc, c, chunk_steps, s);
         if (rc != MRIRT_OK) return rc;
-        rc = inr_forward_dev_n(net, sc.coords, sc.feats, sc.cap, sc.counters + c, sc.classes, sc.counters + kC5MaxPasses + c, s);
+        rc = classify(sc, c, s, ctx);
         if (rc != MRIRT_OK) return rc;
         uint32_t* next = c + 1 < (uint32_t)passes ? sc.counters + c + 1 : nullptr;
         rc = strict ? c5_launch_composite<true>(a, cfg.shade, sc, next, chunk_steps, s)
@@ -511,4 +512,26 @@ extern "C" int mrirt_render_brats_inr(const MrirtBratsParams* p, const MrirtRend
         MRIRT_HIP(hipGetLastError());
     }
     return MRIRT_OK;
+}
+
+}  // namespace mrirt
+
+static int c5_classify_mlp(const C5Scratch& sc, uint32_t c, hipStream_t s, const void* ctx) {
+    return inr_forward_dev_n(static_cast<const MrirtInrDesc*>(ctx), sc.coords, sc.feats, sc.cap, sc.counters + c, sc.classes,
+                             sc.counters + kC5MaxPasses + c, s);
+}
+
+extern "C" int mrirt_render_brats_inr(const MrirtBratsParams* p, const MrirtRenderExt* ext, const void* const vol[4],
+                                      const void* labels, const MrirtInrDesc* net, const float zmu[4], const float zsigma[4],
+                                      uint32_t chunk_steps, void* scratch, int64_t scratch_bytes,
+                                      void* out_rgba, int64_t pitch_px, uint64_t* stats_dev, void* stream) {
+    if (!net) return MRIRT_ERR_NULL;
+    int rc = c5_check_common(ext, vol, zmu, zsigma, scratch, out_rgba);
+    if (rc != MRIRT_OK) return rc;
+    if ((net->kind != MRIRT_INR_FOURIER_RELU && net->kind != MRIRT_INR_SIREN) || net->numMods != 4) return MRIRT_ERR_ARG;
+    // what inr_forward_dev_n would refuse in the first pass, after the plan and the emission had written the scratch
+    if (mrirt_inr_pack_bytes(net) <= 0) return MRIRT_ERR_ARG;
+    if (!net->weights || !net->biases) return MRIRT_ERR_NULL;
+    return c5_frame(p, ext, vol, labels, zmu, zsigma, chunk_steps, scratch, scratch_bytes, out_rgba, pitch_px, stats_dev, stream, INT64_MAX,
+                    c5_classify_mlp, net);
 }

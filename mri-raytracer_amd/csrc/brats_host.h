@@ -43,4 +43,21 @@ int launch_ring_march(const K1Args& a, bool strict, bool shade, hipStream_t s);
 int inr_forward_dev_n(const MrirtInrDesc* desc, const float* coords, const float* feats, int64_t nMax,
                       const uint32_t* nDev, int16_t* argmax, uint32_t* segTicket, hipStream_t s);
 
+// brats_c5.hip: the chunked C5 frame.  Its scratch as c5_carve lays it out, and its frame loop, shared by
+// mrirt_render_brats_inr and mrirt_render_brats_inject (csrc/inr_inject_fused.hip): the two differ only in the classifier a
+// pass enqueues -- classify(sc, pass, stream, ctx) -> status, over sc.coords / sc.feats with the batch size at
+// sc.counters + pass, writing sc.classes.
+struct C5Ray;
+struct C5Scratch { uint32_t* counters; C5Ray* rays; float4* geom; uint2* rowOwner; float* coords; float* feats; float* mix; uint32_t* seg; int16_t* classes; int64_t cap, bytes; };
+constexpr uint32_t kC5MaxPasses = 1024;
+typedef int (*C5Classify)(const C5Scratch& sc, uint32_t pass, hipStream_t s, const void* ctx);
+// what both entry points refuse of their common arguments before they look at their network
+int c5_check_common(const MrirtRenderExt* ext, const void* const vol[4], const float* zmu, const float* zsigma, const void* scratch,
+                    const void* out_rgba);
+// The network was checked by the caller; everything else is refused here, before anything touches the scratch.  maxCap: the
+// largest batch capacity (image x chunk_steps) the classifier takes.
+int c5_frame(const MrirtBratsParams* p, const MrirtRenderExt* ext, const void* const vol[4], const void* labels, const float zmu[4],
+             const float zsigma[4], uint32_t chunk_steps, void* scratch, int64_t scratch_bytes, void* out_rgba, int64_t pitch_px,
+             uint64_t* stats_dev, void* stream, int64_t maxCap, C5Classify classify, const void* ctx);
+
 }  // namespace mrirt

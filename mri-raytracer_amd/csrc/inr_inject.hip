@@ -13,6 +13,7 @@
 #include "inr_device.h"
 #include "inr_gemm.h"
 #include "inr_inject_host.h"
+#include "inr_inject_fused.h"
 #include "edt_line.h"
 #include "siren_sincos.h"
 
@@ -45,11 +46,8 @@ __global__ __launch_bounds__(kInjThreads) void inj_features_kernel(InjFeatArgs a
         cx = sample_coord(x, a.H); cy = sample_coord(y, a.W); cz = sample_coord(z, a.D);
         if (j == 0) { a.coordsOut[3 * i] = cx; a.coordsOut[3 * i + 1] = cy; a.coordsOut[3 * i + 2] = cz; }
     }
-    const float ux = (cx + 1.0f) * 0.5f, uy = (cy + 1.0f) * 0.5f, uz = (cz + 1.0f) * 0.5f;
-    const float p = ((ux * a.B[3 * j]) + (uy * a.B[3 * j + 1])) + (uz * a.B[3 * j + 2]);
-    const float ang = 6.2831855f * p;
     float sn, cs;
-    siren_sincos(ang, sn, cs);
+    inj_feature(cx, cy, cz, a.B[3 * j], a.B[3 * j + 1], a.B[3 * j + 2], sn, cs);      // csrc/inr_inject_fused.h: shared with the fused forward
     a.feat[i * a.F + j] = sn;
     a.feat[i * a.F + half + j] = cs;
 }

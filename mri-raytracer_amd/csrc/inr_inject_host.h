@@ -21,4 +21,11 @@ int inj_run_features(const InjNet& N, const float* B, const float* coords, int64
 int inj_run_layers(const InjNet& N, const float* feat, float* const* act, const float* w, const float* b, const float* coords,
                    const float* mods, int64_t modRow, int64_t modCol, int64_t n, const InjDrop& d, float* logits, hipStream_t s);
 
+// csrc/inr_inject_fused.hip: the fused forward.  inj_fused_check: MRIRT_OK, or what the entry points
+// return for a desc the fused path refuses (no HIP call).  inj_fused_dev_n: one launch over min(*nDev, nMax) rows (nDev NULL:
+// nMax rows), 1 <= nMax < 2^31; argmax or logits may be NULL
+int inj_fused_check(const MrirtInjectDesc* desc);
+int inj_fused_dev_n(const MrirtInjectDesc* desc, const float* B, const float* w, const float* b, const float* coords, const float* mods,
+                    int64_t nMax, const uint32_t* nDev, int16_t* argmax, float* logits, hipStream_t s);
+
 }  // namespace mrirt

@@ -454,6 +454,26 @@ def render_brats_inr(params, intensities, net: PackedMLP, zmu, zsigma, labels=No
     sample in [t0,t1) -> emit -> ONE batched forward -> composite with the class stream); both give the same
     bits, and ``return_aux`` of the one-pass form exposes the emitted inputs and classes for the layered tests.
     """
+    if net.desc.kind not in (KIND_FOURIER_RELU, KIND_SIREN) or net.desc.numMods != 4:
+        raise ValueError("render_brats_inr needs a Fourier/ReLU or SIREN network over 4 modalities "
+                         "(pack_mlp(params, KIND_FOURIER_RELU, K, 4) / pack_mlp(params, KIND_SIREN, 0, 4))")
+    lib = _lib.lib()
+
+    def chunked(P, E, vp, lab, mu, sg, chunk, scratch, o, pitch, st, s):
+        _lib.check(lib.mrirt_render_brats_inr(C.byref(P), C.byref(E), vp, _ptr(lab), C.byref(net.desc), mu, sg, chunk, _ptr(scratch),
+                                              scratch.numel(), _ptr(o), pitch, _ptr(st), s), "mrirt_render_brats_inr")
+
+    def classify_all(coords, feats, total, classes, s):
+        _lib.check(lib.mrirt_inr_forward(C.byref(net.desc), _ptr(coords), _ptr(feats), total, None, _ptr(classes), s), "mrirt_inr_forward")
+
+    return _render_c5("render_brats_inr", params, intensities, zmu, zsigma, labels, out, ext, return_aux, chunk_steps, one_pass, chunked,
+                      classify_all)
+
+
+def _render_c5(who, params, intensities, zmu, zsigma, labels, out, ext, return_aux, chunk_steps, one_pass, chunked, classify_all):
+    """The per-sample INR frame of render_brats_inr / render_brats_inject: binding, the ``chunk_steps=None`` rule, the scratch
+    cache and both forms.  ``chunked(P, E, vp, lab, mu, sg, chunk, scratch, out, pitch, stats, stream)`` enqueues the one-call
+    frame, ``classify_all(coords, feats, total, classes, stream)`` the one batched forward of the ``one_pass`` form."""
     from .render import Grid, _alloc_out, _bind_brats
     dev = _require_gpu()
     if isinstance(intensities, Grid):                    # one "mod4" grid (upload_mod4) carries all four modalities
@@ -463,15 +483,12 @@ def render_brats_inr(params, intensities, net: PackedMLP, zmu, zsigma, labels=No
             raise ValueError("the whole-ray three-pass form marches with the K1 kernels: bind per-modality grids")
         intensities = [intensities] * 4
     if int(params["showPred"]) == 0:
-        raise ValueError("render_brats_inr draws the prediction overlay: set gParams.showPred")
-    if net.desc.kind not in (KIND_FOURIER_RELU, KIND_SIREN) or net.desc.numMods != 4:
-        raise ValueError("render_brats_inr needs a Fourier/ReLU or SIREN network over 4 modalities "
-                         "(pack_mlp(params, KIND_FOURIER_RELU, K, 4) / pack_mlp(params, KIND_SIREN, 0, 4))")
+        raise ValueError(f"{who} draws the prediction overlay: set gParams.showPred")
     P, E, vols, lab, _, _ = _bind_brats(params, intensities, labels, None, ext, dev, pred_stream=True)
     if any(v is None for v in vols):
         raise ValueError("the MLP reads all four modalities: bind gIntensity0..3")
     if E.tileSize > 0:
-        raise ValueError("render_brats_inr renders whole frames")
+        raise ValueError(f"{who} renders whole frames")
     w, h = int(P.imageSize[0]), int(P.imageSize[1])
     lib, s = _lib.lib(), _stream_ptr(None)
     vp = (C.c_void_p * 4)(*[C.c_void_p(t.data_ptr()) for t in vols])
@@ -491,9 +508,7 @@ def render_brats_inr(params, intensities, net: PackedMLP, zmu, zsigma, labels=No
             scratch = _C5_SCRATCH[key] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         o, pitch = _alloc_out(w, h, E, dev, out)
         st = torch.zeros(3, dtype=torch.int64, device=dev) if return_aux else None
-        _lib.check(lib.mrirt_render_brats_inr(C.byref(P), C.byref(E), vp, _ptr(lab), C.byref(net.desc), mu, sg,
-                                              int(chunk_steps), _ptr(scratch), scratch.numel(), _ptr(o), pitch,
-                                              _ptr(st), s), "mrirt_render_brats_inr")
+        chunked(P, E, vp, lab, mu, sg, int(chunk_steps), scratch, o, pitch, st, s)
         if return_aux:
             c = st.cpu()
             return o, dict(live_samples=int(c[0]), shaded_samples=int(c[1]), queries=int(c[2]), chunk_steps=int(chunk_steps))
@@ -509,8 +524,7 @@ def render_brats_inr(params, intensities, net: PackedMLP, zmu, zsigma, labels=No
     _lib.check(lib.mrirt_brats_emit_samples(C.byref(P), C.byref(E), vp, mu, sg, _ptr(offsets), _ptr(coords), _ptr(feats), s),
                "mrirt_brats_emit_samples")
     if total:
-        _lib.check(lib.mrirt_inr_forward(C.byref(net.desc), _ptr(coords), _ptr(feats), total, None, _ptr(classes), s),
-                   "mrirt_inr_forward")
+        classify_all(coords, feats, total, classes, s)
     o, pitch = _alloc_out(w, h, E, dev, out)
     st = torch.zeros(2, dtype=torch.int64, device=dev) if return_aux else None
     _lib.check(lib.mrirt_render_brats_stream(C.byref(P), C.byref(E), vp, _ptr(lab), _ptr(classes), _ptr(offsets),
@@ -1589,6 +1603,67 @@ def inject_forward(params, coords, mods, *, dropout: Optional[_lib.InjectDropout
                                          _ptr(am) if am is not None else None, _ptr(scratch), nbytes, _stream_ptr(None))
     _lib.check(rc, "mrirt_inject_forward")
     return (logits, am) if want_argmax else logits
+
+
+def inject_fused_ok(params, coord_layers=(1, 2, 3), mod_layers=(2,)) -> bool:
+    """Whether the fused forward (``inject_classify``, ``render_brats_inject``) takes this network: its weights, padded, and the
+    waves' buffers fit the 160 KiB of LDS of one compute unit.  No GPU needed."""
+    desc = inject_desc(params, coord_layers, mod_layers)
+    return int(_lib.lib().mrirt_inject_fused_lds_bytes(C.byref(desc))) > 0
+
+
+def inject_classify(params, coords, mods, *, count: Optional[torch.Tensor] = None, want_logits: bool = False, coord_layers=(1, 2, 3),
+                    mod_layers=(2,)):
+    """The int16 class per point of ``inject_forward(..., want_argmax=True)`` without dropout -- the same bits -- in ONE launch
+    (``mrirt_inject_classify``: the network stays in LDS, nothing but coords, mods and the outputs touches memory).  ``count``: a
+    one-element int32 / uint32 device tensor; the kernel then processes ``min(count, n)`` rows and leaves the other rows of the
+    outputs as they were allocated (zero).  ``want_logits``: also the logits (n, C).  A shape the fused path refuses
+    (``inject_fused_ok``) raises."""
+    dev = _require_gpu()
+    desc = inject_desc(params, coord_layers, mod_layers)
+    c, m = _inject_points(coords, mods, dev, desc.numMods)
+    n = c.shape[0]
+    if count is not None and (count.numel() != 1 or count.dtype not in (torch.int32, torch.uint32) or not count.is_cuda):
+        raise ValueError("inject_classify: count is a one-element int32 / uint32 device tensor")
+    B, w, b = _inject_flat(params, dev)
+    am = torch.zeros(n, dtype=torch.int16, device=dev)
+    logits = torch.zeros((n, desc.width[desc.numLayers - 1]), dtype=torch.float32, device=dev) if want_logits else None
+    rc = _lib.lib().mrirt_inject_classify(C.byref(desc), _ptr(B), _ptr(w), _ptr(b), _ptr(c), _ptr(m) if m is not None else None, n,
+                                          _ptr(count) if count is not None else None, _ptr(am),
+                                          _ptr(logits) if logits is not None else None, _stream_ptr(None))
+    _lib.check(rc, "mrirt_inject_classify")
+    return (am, logits) if want_logits else am
+
+
+def render_brats_inject(params, intensities, net_params, zmu, zsigma, labels=None, out=None, ext=None, return_aux: bool = False,
+                        chunk_steps: Optional[int] = None, one_pass: bool = False, coord_layers=(1, 2, 3), mod_layers=(2,)):
+    """``render_brats_inr`` with the coordinate-injection network ``net_params`` (``inject_load`` / ``train_inject``; four
+    modalities): the prediction overlay's label is the net evaluated AT every live march sample.  Default:
+    ``mrirt_render_brats_inject``, the chunked ERT-aware frame whose passes are classified by the fused forward, the batch size
+    read from device memory; the same ``chunk_steps=None`` rule and scratch cache.  ``one_pass=True`` is the whole-ray form built
+    from ``mrirt_brats_sample_counts``, ``mrirt_brats_emit_samples``, ``mrirt_inject_forward`` (argmax) and
+    ``mrirt_render_brats_stream``: the definition the chunked frame is tested against, with the same ``aux``."""
+    dev = _require_gpu()
+    desc = inject_desc(net_params, coord_layers, mod_layers)
+    if desc.numMods != 4:
+        raise ValueError("render_brats_inject needs a coordinate-injection network over 4 modalities")
+    lib = _lib.lib()
+    if not one_pass and int(lib.mrirt_inject_fused_lds_bytes(C.byref(desc))) <= 0:
+        raise ValueError("render_brats_inject: the fused forward refuses this shape (inject_fused_ok)")
+    B, w, b = _inject_flat(net_params, dev)
+
+    def chunked(P, E, vp, lab, mu, sg, chunk, scratch, o, pitch, st, s):
+        _lib.check(lib.mrirt_render_brats_inject(C.byref(P), C.byref(E), vp, _ptr(lab), C.byref(desc), _ptr(B), _ptr(w), _ptr(b), mu, sg,
+                                                 chunk, _ptr(scratch), scratch.numel(), _ptr(o), pitch, _ptr(st), s),
+                   "mrirt_render_brats_inject")
+
+    def classify_all(coords, feats, total, classes, s):
+        scratch, nbytes = _inject_scratch(desc, total, dev)
+        _lib.check(lib.mrirt_inject_forward(C.byref(desc), _ptr(B), _ptr(w), _ptr(b), _ptr(coords), _ptr(feats), total, None, None,
+                                            _ptr(classes), _ptr(scratch), nbytes, s), "mrirt_inject_forward")
+
+    return _render_c5("render_brats_inject", params, intensities, zmu, zsigma, labels, out, ext, return_aux, chunk_steps, one_pass, chunked,
+                      classify_all)
 
 
 def compute_uncertainty_mc_dropout(params, coords, mods, n_samples: int = 5, seed: int = 0, dropout_rate: float = 0.3, *,
